@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Throughput of the MI355X StereoAnywhere forward on synthetic 540x960 pairs.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config cfg2|cfg4|cfg3|cfg5]
+    python bench.py [--gpus N --steps K --warmup W] [--config cfg2|cfg4|cfg3|cfg5] [--full]
+                    [--dump-outputs DIR]
         (N > 1 without torchrun: bench.py starts the N ranks itself, one child process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -12,7 +13,14 @@ is all-pairs over W/4), configs[1]: batch 4 per GPU, padded to 544
 A step = one test_mode forward over the rank's batch, inputs resident in HBM.
 Weak scaling: every rank runs its own batch of 4; value = all pairs / max-over-ranks time.
 
-Also reported (rank 0):
+A plain run sets up, warms up (W steps, then the execution probe that picks hipGraph replay or eager
+launches for the timed steps), times the K steps, writes the last step's output with --dump-outputs
+(DIR/flow_up.npy, float32; the tiled configs: DIR/disparity.npy) and prints the line: value,
+ms_per_step (the timed region / K) and the workload's description.  Inputs and weights are seeded,
+so two builds run with the same arguments see identical inputs.
+
+With --full also measured after the timed steps and reported (rank 0), beside the other execution
+mode's time (eager_ms_per_step), the bit-for-bit graph-vs-eager check and the box state:
   roofline      the dominant hand-written kernel, timed live with HIP events on its
                 launch stream inside the timed region (libsa_hip sa_timing_*),
                 algorithmic bytes or flops per launch / mean launch time vs MI355X peak
@@ -25,7 +33,7 @@ Also reported (rank 0):
                  same step otherwise; at world size 8 the global batch is configs[3]'s 64, below it
                  the line is configs[3]'s per-rank workload (the scaling curve needs an 8-GPU node)
 
-Box state: the GPU's sysfs clock levels, power and temperatures before and after the timed
+Box state (--full): the GPU's sysfs clock levels, power and temperatures before and after the timed
 region, and sclk / power sampled every 100 ms during it (box_state; the run-to-run spread of
 the headline is attributed against these).
 
@@ -36,7 +44,7 @@ Tiled configs (separate lines, not the headline):
                  (1120x896 tiles, overlap 224) under CPUOffloadWrapper: 25 tiles, 32 iterations
   A step = one image through the tiler (TileWrapper with batch_tiles, the reference's own
   option: every tile has the preset's size, so the tiles run as one batch), stitched.
-  epe_vs_reference  EPE of this build vs the reference's own disparity (golden vector,
+  epe_vs_reference  (--full) EPE of this build vs the reference's own disparity (golden vector,
                 544x960, 22 iterations) on identical inputs and weights
 """
 from __future__ import annotations
@@ -452,6 +460,90 @@ def self_launch(gpus: int):
     return 0
 
 
+def roofline_report(work, kt, shape, iters, steps, traffic_batch, elapsed_1s, one_stream_steps, elapsed_ev):
+    """--full: the roofline key of the line.  work: the per-call priced families of one forward
+    (ops.WORK); kt: {kernel: (total ms, launches)} of the instrumented steps; traffic_batch: the batch
+    whose committed PMC pass gives the dominant kernel's HBM bytes (None: the tiled configs)."""
+    # every hand-written kernel family: algorithmic work / live event time vs MI355X peak
+    costs = step_costs(shape[0], shape[1], shape[2], iters)
+    costs["conv2d_wino"] = ("TFLOP/s", work.get("conv2d_wino", 0.0))
+    costs["conv2d_wino4"] = ("TFLOP/s", work.get("conv2d_wino4", 0.0))
+    costs["conv2d_direct"] = ("TFLOP/s", work.get("conv2d_direct", 0.0))
+    costs["norm_act"] = ("GB/s", work.get("norm_act", 0.0))
+    # the separate GRU gate kernels run only at levels whose width keeps the gates out of the
+    # F(4x4) epilogues (W % 4 != 0): priced per call (ops.gru_zr / gru_out, 9 resp. 6-7 planes)
+    costs["gru_zr"] = ("GB/s", work.get("gru_zr", 0.0))
+    costs["gru_out"] = ("GB/s", work.get("gru_out", 0.0))
+    # the update loop's plumbing (pool2x / interp / flow_update: planes read and written once),
+    # flow_head.conv2 (256 -> 2 planes), the mono pyramid (volume read, levels written) and convf1
+    # (7x7, 2 -> 64 channels on fp32 MFMA), each priced per call (ops._account)
+    for k_, u_ in (("gru_plumbing", "GB/s"), ("conv2d_narrow", "GB/s"), ("mono_pyramid", "GB/s"), ("conv1x1", "GB/s"),
+                   ("conv2d_small", "TFLOP/s")):
+        costs[k_] = (u_, work.get(k_, 0.0))
+    kernels = {}
+    for k, (ms_tot, n_launch) in kt.items():
+        if n_launch == 0 or k not in costs:
+            continue
+        unit, amount = costs[k]
+        secs = ms_tot / 1e3 / steps                      # per step
+        if unit == "TFLOP/s":
+            ach, peak, bound = amount / secs / 1e12, FP32_MFMA_PEAK_TFS, "mfma"
+            split4 = (k == "conv2d_wino4" and ops.W4_SPLIT) or (k == "conv2d_direct" and ops.DIRECT_SPLIT)
+        else:
+            ach, peak, bound = amount / secs / 1e9, HBM_PEAK_GBS, "hbm"
+            split4 = False
+        kernels[k] = {"bound": bound, "achieved": ach, "peak": peak, "unit": unit, "frac": ach / peak,
+                      "ms_per_step": ms_tot / steps, "launches_per_step": n_launch / steps,
+                      "avg_launch_us": ms_tot * 1e3 / n_launch}
+        if split4:
+            # the split kernels' fp32 products (path type, peak 157.3 TF/s from the guide) also against
+            # the 16x16x16 f16 form's fp32-product rate (2x, self-derived) and as issued f16 flops (4
+            # f16 products per fp32 one) against the F16 dense peak (~2.5 PF)
+            kernels[k].update(split_peak=SPLIT_MFMA_PEAK_TFS, frac_split_peak=ach / SPLIT_MFMA_PEAK_TFS,
+                              f16_issued_tflops=4 * ach, frac_f16_dense_peak=4 * ach / F16_DENSE_PEAK_TFS)
+    dom = max(kernels, key=lambda k: kernels[k]["ms_per_step"])
+    roof = dict(kernels[dom])
+    roof.update({"kernel": dom, "traffic": pmc_traffic(dom, traffic_batch) if traffic_batch is not None else None,
+                 "kernels": kernels, "misc_ms_per_step": kt["misc"][0] / steps,
+                 "schedule": "one-stream (model.stream_overlap = False)",
+                 "one_stream_ms_per_step": elapsed_1s / steps * 1e3,
+                 "one_stream_step_ms": one_stream_steps,
+                 "instrumented_ms_per_step": elapsed_ev / steps * 1e3,
+                 "note": "achieved = algorithmic amount per launch / mean live HIP-event launch time, "
+                         "events recorded around every launch over K steps run right after the K "
+                         "plain timed steps (the events cost ~6 % of a step), in the one-stream order "
+                         "(model.stream_overlap = False, the whole batch per launch; its plain time is "
+                         "one_stream_ms_per_step; the headline steps overlap the mono branch and the "
+                         "context encoder with the feature encoder on side streams and run the GRU loop "
+                         "as two batch parts on two streams, replayed from a hipGraph); "
+                         "conv3d_fused counts the direct 3x3x3 convolutions' flops (its stride-1 "
+                         "convs execute half of them: F(4,3) Winograd along D); "
+                         "fp32 FMA peak 157.3 TF/s is the same for MFMA (v_mfma_f32_*_f32) and VALU; "
+                         "conv2d_wino / conv2d_wino4 count the Winograd-domain products they execute "
+                         "(16/36 resp. 36/144 of the direct convolution's), so their direct-equivalent "
+                         "rates are 2.25x resp. 4x achieved"
+                         + ("; conv2d_wino4 / conv2d_direct run the split kernels (ops.W4_SPLIT, "
+                            "ops.DIRECT_SPLIT): achieved = their fp32 products (exact f16 hi/lo pair "
+                            "products) against the guide's fp32 matrix peak 157.3 TF/s; split_peak "
+                            "(2x, the 16x16x16 f16 form) and the issued f16 flops vs the F16 dense peak "
+                            "are side fields" if ops.W4_SPLIT or ops.DIRECT_SPLIT else "")})
+    return roof
+
+
+def dump_outputs(directory, out, tiled, r):
+    """--dump-outputs: what the last timed step returned to its caller, as float32 .npy files:
+    flow_up [B, 1, H, W] (= -disparity) of the model's (flow_up, None), or the tiler's stitched
+    disparity [1, 1, H, W].  The configs' own outputs fit whole (cfg5, 3008 x 4128: 50 MB); a larger
+    one (--batch) is written as a seeded sample of 2^24 of its elements (the same ones every run)."""
+    os.makedirs(directory, exist_ok=True)
+    arr = (out[0] if isinstance(out, tuple) else out).detach().float().cpu().numpy()
+    if arr.nbytes > 64 << 20:
+        arr = arr.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, arr.size, 1 << 24))]
+    name = ("disparity" if tiled else "flow_up") + (f".rank{r.rank}" if r.world > 1 else "")
+    np.save(os.path.join(directory, name + ".npy"), arr)
+    log(f"wrote {name}.npy {arr.shape} to {directory}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -503,10 +595,20 @@ def main():
                          "timed beside it)")
     ap.add_argument("--wino4-min-blocks", type=int, default=None,
                     help="F(4x4) for launches of at least this many blocks (default: ops._WINO4_MIN_BLOCKS)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the headline: the "
+                         "roofline (per-kernel event times, one-stream steps), the other execution mode and the "
+                         "graph-vs-eager check, the box state, the EPE against the reference and the CPU "
+                         "baseline (--no-epe / --no-cpu-baseline leave those two out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32; with more than "
+                         "one rank, DIR/<name>.rank<r>.npy)")
     ap.add_argument("--dry-run", action="store_true",
                     help="rendezvous only: every rank joins the process group and rank 0 prints the ranks that "
                          "reported (checks the multi-rank launch without a model or a GPU)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the timed region over the steps)")
     # --gpus N > 1 without a torchrun environment: this process becomes the launcher of N ranks
     # (before anything touches the GPU); under torchrun the world size must match --gpus
     rc = self_launch(args.gpus)
@@ -541,7 +643,7 @@ def main():
             if r.world > 1:
                 line["rank_timing"] = rank_report(per_rank, args.steps, gather_ms, got.numel() * 8,
                                                   os.environ.get("SA_DIST_BACKEND", "nccl"))
-            if not args.no_cpu_baseline:   # (a tiny oracle sample: the key's plumbing, not a baseline)
+            if args.full and not args.no_cpu_baseline:   # (a tiny oracle sample: the key's plumbing, not a baseline)
                 line["cpu_baseline"] = cpu_baseline(1, 64, 128, runs=1, cfg1=False)
             print(json.dumps(line))
         return
@@ -655,18 +757,22 @@ def main():
             if t_eager < t_graph:
                 graph_runner, runner = runner, eager_runner
                 log("timed steps run eagerly (faster on this box)")
-        # price the layer-mix-dependent families (Winograd convs, norm epilogues) on one
+        # --full: price the layer-mix-dependent families (Winograd convs, norm epilogues) on one
         # untimed forward
-        from stereoanywhere_amd import ops as O
-        O.WORK = {}
-        eager_step()
-        work, O.WORK = O.WORK, None
-        torch.cuda.synchronize()
+        work = {}
+        if args.full:
+            from stereoanywhere_amd import ops as O
+            O.WORK = {}
+            eager_step()
+            work, O.WORK = O.WORK, None
+            torch.cuda.synchronize()
         # timed region: K plain steps -> value.  The per-launch HIP events of the roofline
-        # serialise every launch (~6 % of a step), so they run over K more steps right after.
-        sysd = _gpu_sysfs(device)
+        # serialise every launch (~6 % of a step), so they run over K more steps right after (--full).
+        # The box state (sysfs snapshots, the sampler thread, the clock probe) is read under --full only.
+        sysd = _gpu_sysfs(device) if args.full else None
         state_before = box_state(sysd) or {}
-        state_before.update(clock_probe(device))
+        if args.full:
+            state_before.update(clock_probe(device))
         N.lib().sa_split_redo_blocks(1)   # (synchronises; outside the timed region)
         D.barrier(r)
         torch.cuda.synchronize()
@@ -679,67 +785,69 @@ def main():
             D.barrier(r)
             elapsed = time.perf_counter() - t0
         redo_blocks = int(N.lib().sa_split_redo_blocks(1))
-        state_after = box_state(sysd) or {}
-        state_after.update(clock_probe(device))
         log(f"timed {args.steps} steps in {elapsed:.3f} s")
-        # cfg5: the other CPUOffloadWrapper cache policy over the same steps (the reference empties the
-        # allocator cache after every call, cpu_offload_wrapper.py:82)
-        other_release = None
-        if tiled is not None and tiled["offload"]:
-            runner.release_cache = not runner.release_cache
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out, tiled is not None, r)
+        other_release, graph_dev = None, None
+        if args.full:
+            state_after = box_state(sysd) or {}
+            state_after.update(clock_probe(device))
+            # cfg5: the other CPUOffloadWrapper cache policy over the same steps (the reference empties the
+            # allocator cache after every call, cpu_offload_wrapper.py:82)
+            if tiled is not None and tiled["offload"]:
+                runner.release_cache = not runner.release_cache
+                torch.cuda.synchronize()
+                t4 = time.perf_counter()
+                for _ in range(args.steps):
+                    step()
+                torch.cuda.synchronize()
+                other_release = {"release_cache": runner.release_cache,
+                                 "ms_per_step": (time.perf_counter() - t4) / args.steps * 1e3}
+                runner.release_cache = not runner.release_cache
+                log(f"release_cache={other_release['release_cache']}: {other_release['ms_per_step']:.1f} ms/step")
+            # the same steps launched eagerly (no graph), for the record (or, when the probe chose
+            # eager steps, replayed from the graph)
+            other = graph_runner if graph_runner is not None else eager_runner
             torch.cuda.synchronize()
-            t4 = time.perf_counter()
+            t3 = time.perf_counter()
             for _ in range(args.steps):
-                step()
+                out_e = other(*x, iters=iters, test_mode=True)
             torch.cuda.synchronize()
-            other_release = {"release_cache": runner.release_cache,
-                             "ms_per_step": (time.perf_counter() - t4) / args.steps * 1e3}
-            runner.release_cache = not runner.release_cache
-            log(f"release_cache={other_release['release_cache']}: {other_release['ms_per_step']:.1f} ms/step")
-        # the same steps launched eagerly (no graph), for the record (or, when the probe chose
-        # eager steps, replayed from the graph)
-        other = graph_runner if graph_runner is not None else eager_runner
-        torch.cuda.synchronize()
-        t3 = time.perf_counter()
-        for _ in range(args.steps):
-            out_e = other(*x, iters=iters, test_mode=True)
-        torch.cuda.synchronize()
-        elapsed_other = time.perf_counter() - t3
-        elapsed_eager = elapsed if runner is eager_runner else elapsed_other
-        graph_dev = None
-        if runner is not other:   # the replayed forward is the eager one
-            graph_dev = float((out[0] - out_e[0]).abs().max())
-            if graph_dev != 0.0:
-                raise SystemExit(f"bench: the hipGraph replay differs from the eager forward by {graph_dev:g} "
-                                 "(it must compute the same function bit for bit); no throughput reported")
-        # one-stream plain steps: the schedule the per-launch times below are measured in.  One
-        # untimed step first: the whole batch per launch is a new set of shapes (allocator
-        # growth, MIOpen kernels built on first use: cfg5's first one-stream steps ran 2.7x slow)
-        model.stream_overlap = False
-        eager_step()
-        torch.cuda.synchronize()
-        t2 = time.perf_counter()
-        one_stream_steps = []
-        for _ in range(args.steps):
-            ts = time.perf_counter()
+            elapsed_other = time.perf_counter() - t3
+            elapsed_eager = elapsed if runner is eager_runner else elapsed_other
+            if runner is not other:   # the replayed forward is the eager one
+                graph_dev = float((out[0] - out_e[0]).abs().max())
+                if graph_dev != 0.0:
+                    raise SystemExit(f"bench: the hipGraph replay differs from the eager forward by {graph_dev:g} "
+                                     "(it must compute the same function bit for bit); no throughput reported")
+            # one-stream plain steps: the schedule the per-launch times below are measured in.  One
+            # untimed step first: the whole batch per launch is a new set of shapes (allocator
+            # growth, MIOpen kernels built on first use: cfg5's first one-stream steps ran 2.7x slow)
+            model.stream_overlap = False
             eager_step()
             torch.cuda.synchronize()
-            one_stream_steps.append((time.perf_counter() - ts) * 1e3)
-        elapsed_1s = time.perf_counter() - t2
-        log("one-stream steps (ms): " + ", ".join(f"{v:.1f}" for v in one_stream_steps))
-        # per-launch times of one kernel at a time: the side streams' overlap (model.py) would
-        # stretch each launch by the work running beside it
-        N.timing_enable(True)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            eager_step()
-        torch.cuda.synchronize()
-        elapsed_ev = time.perf_counter() - t1
-        kt = {k: N.timing_read(k) for k in N.KERNEL_IDS}
-        N.timing_enable(False)
-        model.stream_overlap = not args.one_stream
-        log(f"instrumented {args.steps} steps in {elapsed_ev:.3f} s")
+            t2 = time.perf_counter()
+            one_stream_steps = []
+            for _ in range(args.steps):
+                ts = time.perf_counter()
+                eager_step()
+                torch.cuda.synchronize()
+                one_stream_steps.append((time.perf_counter() - ts) * 1e3)
+            elapsed_1s = time.perf_counter() - t2
+            log("one-stream steps (ms): " + ", ".join(f"{v:.1f}" for v in one_stream_steps))
+            # per-launch times of one kernel at a time: the side streams' overlap (model.py) would
+            # stretch each launch by the work running beside it
+            N.timing_enable(True)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                eager_step()
+            torch.cuda.synchronize()
+            elapsed_ev = time.perf_counter() - t1
+            kt = {k: N.timing_read(k) for k in N.KERNEL_IDS}
+            N.timing_enable(False)
+            model.stream_overlap = not args.one_stream
+            log(f"instrumented {args.steps} steps in {elapsed_ev:.3f} s")
         per_rank = D.gather_scalars(own, r, device)
         elapsed = D.max_over_ranks(elapsed, r, device)
         # per-unit metrics gathered once, after the timed region (the only data-path collective)
@@ -755,70 +863,6 @@ def main():
     total_units = units * r.world * args.steps
     if not r.is_main:
         return
-    # every hand-written kernel family: algorithmic work / live event time vs MI355X peak
-    costs = step_costs(shape[0], shape[1], shape[2], iters)
-    costs["conv2d_wino"] = ("TFLOP/s", work.get("conv2d_wino", 0.0))
-    costs["conv2d_wino4"] = ("TFLOP/s", work.get("conv2d_wino4", 0.0))
-    costs["conv2d_direct"] = ("TFLOP/s", work.get("conv2d_direct", 0.0))
-    costs["norm_act"] = ("GB/s", work.get("norm_act", 0.0))
-    # the separate GRU gate kernels run only at levels whose width keeps the gates out of the
-    # F(4x4) epilogues (W % 4 != 0): priced per call (ops.gru_zr / gru_out, 9 resp. 6-7 planes)
-    costs["gru_zr"] = ("GB/s", work.get("gru_zr", 0.0))
-    costs["gru_out"] = ("GB/s", work.get("gru_out", 0.0))
-    # the update loop's plumbing (pool2x / interp / flow_update: planes read and written once),
-    # flow_head.conv2 (256 -> 2 planes), the mono pyramid (volume read, levels written) and convf1
-    # (7x7, 2 -> 64 channels on fp32 MFMA), each priced per call (ops._account)
-    for k_, u_ in (("gru_plumbing", "GB/s"), ("conv2d_narrow", "GB/s"), ("mono_pyramid", "GB/s"), ("conv1x1", "GB/s"),
-                   ("conv2d_small", "TFLOP/s")):
-        costs[k_] = (u_, work.get(k_, 0.0))
-    kernels = {}
-    for k, (ms_tot, n_launch) in kt.items():
-        if n_launch == 0 or k not in costs:
-            continue
-        unit, amount = costs[k]
-        secs = ms_tot / 1e3 / args.steps                      # per step
-        if unit == "TFLOP/s":
-            ach, peak, bound = amount / secs / 1e12, FP32_MFMA_PEAK_TFS, "mfma"
-            split4 = (k == "conv2d_wino4" and ops.W4_SPLIT) or (k == "conv2d_direct" and ops.DIRECT_SPLIT)
-        else:
-            ach, peak, bound = amount / secs / 1e9, HBM_PEAK_GBS, "hbm"
-            split4 = False
-        kernels[k] = {"bound": bound, "achieved": ach, "peak": peak, "unit": unit, "frac": ach / peak,
-                      "ms_per_step": ms_tot / args.steps, "launches_per_step": n_launch / args.steps,
-                      "avg_launch_us": ms_tot * 1e3 / n_launch}
-        if split4:
-            # the split kernels' fp32 products (path type, peak 157.3 TF/s from the guide) also against
-            # the 16x16x16 f16 form's fp32-product rate (2x, self-derived) and as issued f16 flops (4
-            # f16 products per fp32 one) against the F16 dense peak (~2.5 PF)
-            kernels[k].update(split_peak=SPLIT_MFMA_PEAK_TFS, frac_split_peak=ach / SPLIT_MFMA_PEAK_TFS,
-                              f16_issued_tflops=4 * ach, frac_f16_dense_peak=4 * ach / F16_DENSE_PEAK_TFS)
-    dom = max(kernels, key=lambda k: kernels[k]["ms_per_step"])
-    roof = dict(kernels[dom])
-    roof.update({"kernel": dom, "traffic": pmc_traffic(dom, args.batch) if tiled is None else None,
-                 "kernels": kernels, "misc_ms_per_step": kt["misc"][0] / args.steps,
-                 "schedule": "one-stream (model.stream_overlap = False)",
-                 "one_stream_ms_per_step": elapsed_1s / args.steps * 1e3,
-                 "one_stream_step_ms": one_stream_steps,
-                 "instrumented_ms_per_step": elapsed_ev / args.steps * 1e3,
-                 "note": "achieved = algorithmic amount per launch / mean live HIP-event launch time, "
-                         "events recorded around every launch over K steps run right after the K "
-                         "plain timed steps (the events cost ~6 % of a step), in the one-stream order "
-                         "(model.stream_overlap = False, the whole batch per launch; its plain time is "
-                         "one_stream_ms_per_step; the headline steps overlap the mono branch and the "
-                         "context encoder with the feature encoder on side streams and run the GRU loop "
-                         "as two batch parts on two streams, replayed from a hipGraph); "
-                         "conv3d_fused counts the direct 3x3x3 convolutions' flops (its stride-1 "
-                         "convs execute half of them: F(4,3) Winograd along D); "
-                         "fp32 FMA peak 157.3 TF/s is the same for MFMA (v_mfma_f32_*_f32) and VALU; "
-                         "conv2d_wino / conv2d_wino4 count the Winograd-domain products they execute "
-                         "(16/36 resp. 36/144 of the direct convolution's), so their direct-equivalent "
-                         "rates are 2.25x resp. 4x achieved"
-                         + ("; conv2d_wino4 / conv2d_direct run the split kernels (ops.W4_SPLIT, "
-                            "ops.DIRECT_SPLIT): achieved = their fp32 products (exact f16 hi/lo pair "
-                            "products) against the guide's fp32 matrix peak 157.3 TF/s; split_peak "
-                            "(2x, the 16x16x16 f16 form) and the issued f16 flops vs the F16 dense peak "
-                            "are side fields" if ops.W4_SPLIT or ops.DIRECT_SPLIT else "")
-})
     if tiled is None:
         metric, unit = "stereo pairs/sec @540x960 D=192 (1/2/4/8 GPU) + EPE vs reference", "pairs/s"
         if args.config == "cfg4":
@@ -851,19 +895,23 @@ def main():
                   + " products as exact f16 hi/lo pair products on MFMA, fp32 accumulation; everything else "
                   "fp32)" if ops.W4_SPLIT or ops.DIRECT_SPLIT else "f32"), "data": "synthetic (seeded value-noise pairs, "
         "seeded random weights; no dataset/checkpoint offline)",
-        "config": config, "roofline": roof, "gathered_units": int(allm.shape[0]),
+        "config": config, "gathered_units": int(allm.shape[0]),
         "execution": ("eager launches, chosen over hipGraph replay by the untimed execution probe"
                       if graph_runner is not None else
                       "hipGraph replay of the whole forward (stereoanywhere_amd.graph.ForwardGraph; inputs "
-                      "copied into its static buffers each step)" if graph_dev is not None else "eager launches"),
-        "eager_ms_per_step": elapsed_eager / args.steps * 1e3,
+                      "copied into its static buffers each step)" if runner is not eager_runner else "eager launches"),
         "execution_probe": probe,
         # split-kernel blocks the f16 range guard recomputed on fp32 MFMA during the timed steps
         "split_redo_blocks": redo_blocks,
         "split_guard": bool(ops.SPLIT_GUARD),
         "schedule_overrides": args.opts or None,
-        "box_state": {"before": state_before, "during": sampler.summary(), "after": state_after},
+        "full": bool(args.full),
     }
+    if args.full:
+        res["roofline"] = roofline_report(work, kt, shape, iters, args.steps, args.batch if tiled is None else None,
+                                          elapsed_1s, one_stream_steps, elapsed_ev)
+        res["eager_ms_per_step"] = elapsed_eager / args.steps * 1e3
+        res["box_state"] = {"before": state_before, "during": sampler.summary(), "after": state_after}
     if graph_dev is not None:
         res["graph_vs_eager_max_abs"] = graph_dev
     if tiled is not None:
@@ -871,14 +919,14 @@ def main():
             res["offload_other_release_cache"] = other_release
         res["tiles_per_s"] = total_units * tiled["tiles"] / elapsed
         res["unique_tile_forwards_per_s"] = total_units * tiled["unique_tiles"] / elapsed
-    if not args.no_epe:
+    if args.full and not args.no_epe:
         res["epe_vs_reference"] = (epe_vs_reference(model, device) if tiled is None
                                    else epe_vs_reference_tiled(model, device, args.config))
         log(f"EPE vs reference {res['epe_vs_reference']:.3g}")
     if r.world > 1:
         res["rank_timing"] = rank_report(per_rank, args.steps, gather_ms, allm.numel() * 8,
                                          os.environ.get("SA_DIST_BACKEND", "nccl"))
-    if not args.no_cpu_baseline:   # (rank 0, after every collective: the other ranks are not held)
+    if args.full and not args.no_cpu_baseline:   # (rank 0, after every collective: the other ranks are not held)
         log("cpu baseline (oracle, bounded sample) ...")
         res["cpu_baseline"] = cpu_baseline(iters, Hp, Wp) if tiled is None else cpu_baseline_tile(tiled, iters)
     print(json.dumps(res))

@@ -8,7 +8,7 @@ mkdir -p gpurun_out/rehearsal
 steps=(
   "rh_tests:900:python -u -m pytest tests -x -q -m gpu --timeout 300 --timeout-method thread"
   "rh_smoke:300:python -c 'import __graft_entry__ as g; g.smoke(); print(\"smoke ok\")'"
-  "rh_bench:420:python bench.py"
+  "rh_bench:420:python bench.py --full"
 )
 bash "$R/scripts/gpu_steps.sh" "${steps[@]}"
 rc=$?

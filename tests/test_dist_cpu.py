@@ -150,9 +150,10 @@ def test_bench_launches_its_own_ranks(world):
     the process group and reports world == N (the --dry-run rendezvous, gloo on the CPU).  The line
     explains itself at N > 1: each rank's timed-region ms per step (stand-in
     steps: rank r sleeps 5 (r + 1) ms, so the last rank is the slowest), the metric all_gather's
-    latency and size, and the cpu_baseline key (a tiny oracle sample in the dry run)."""
+    latency and size, and the cpu_baseline key (a tiny oracle sample in the dry run; the baseline is
+    part of bench.py --full)."""
     import json
-    res = _bench(["--gpus", str(world), "--dry-run", "--steps", "3"])
+    res = _bench(["--gpus", str(world), "--dry-run", "--steps", "3", "--full"])
     assert res.returncode == 0, res.stderr
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == world
