@@ -247,7 +247,9 @@ int sa_flow_update(float *coords_x, const float *delta, long delta_bs, int B, in
 /* a10 + update.py:75, 84 — the lookup of sa_corr_lookup fused with the motion encoder's convc1
  * (1x1 conv of the L*(2r+1) taps -> Cout, + bias, ReLU): weight_kc [L*(2r+1)][Cout] (the
  * module's [Cout][K][1][1] transposed), out [B*nvol, Cout, H, W1] with sample b*nvol + v
- * (v = 0 for pyramid_a, 1 for pyramid_b).  Built for 4 levels, radius 4, Cout 64. */
+ * (v = 0 for pyramid_a, 1 for pyramid_b).  Built for 1..4 levels, radius 1..8, Cout 64: (4, 4) on
+ * kernel instances of its own, every other pair on one tap-folding kernel (acc = bias, then
+ * acc = fmaf(w[k], tap[k], acc) for k ascending, the same chain). */
 int sa_corr_lookup_conv1x1(const float *pyramid_a, const float *pyramid_b, int W2, long row_stride,
                            int num_levels, int radius, const float *coords_x, long coords_bstride,
                            int B, int H, int W1, const float *weight_kc, const float *bias, int Cout,
@@ -264,7 +266,7 @@ int sa_corr_lookup_conv1x1(const float *pyramid_a, const float *pyramid_b, int W
  *   sa_corr_pyramid_from_volume_strided_sheared: sa_corr_pyramid_from_volume_strided written
  *     sheared
  *   sa_corr_lookup_conv1x1_sheared: sa_corr_lookup_conv1x1 on sheared pyramids (same taps,
- *     same arithmetic; 4 levels, radius 4, Cout 64). */
+ *     same arithmetic, bit for bit; 1..4 levels, radius 1..8, Cout 64). */
 /* convc1 of the fused lookups (both layouts) on the VALU (0, default) or fp32 MFMA (1, measured
  * slower): the same k-ordered fmaf chain either way.  For A/B runs and tests. */
 void sa_lookup_set_mfma(int on);
@@ -277,7 +279,7 @@ int sa_lookup_get_shear_dual(void);
 long sa_shear_slice_size(int W1, int W2, int num_levels);
 long sa_shear_row_pitch(int W1);
 /* 1 when sa_corr_pyramid_shear + sa_corr_lookup_conv1x1_sheared take this geometry (B*H <= 65535,
- * W2 <= 511, 4 levels with the coarsest >= 2 wide), else 0: the caller keeps the row layout */
+ * W2 <= 511, 1..4 levels with the coarsest >= 2 wide), else 0: the caller keeps the row layout */
 int sa_corr_shear_supported(int B, int H, int W1, int W2, int num_levels);
 long sa_shear_level_offset(int W1, int W2, int num_levels, int level);
 int sa_corr_pyramid_shear(const float *pyramid, long row_stride, int B, int H, int W1, int W2,

@@ -91,13 +91,17 @@ class MultiBasicEncoder(nn.Module):
             [nn.Sequential(ResidualBlock(128, 128, norm_fn), nn.Conv2d(128, d[1], 3, padding=1)) for d in output_dim])
         self.outputs32 = nn.ModuleList([nn.Conv2d(128, d[0], 3, padding=1) for d in output_dim])
 
-    def forward(self, x) -> List[List[torch.Tensor]]:
+    def forward(self, x, num_layers: int = 3) -> List[List[torch.Tensor]]:
+        """The heads of the first num_layers levels (extractor.py:275-300)."""
         x = self.relu1(self.norm1(self.conv1(x)))
         s08 = self.layer3(self.layer2(self.layer1(x)))
-        s16 = self.layer4(s08)
-        s32 = self.layer5(s16)
-        return [[f(s08) for f in self.outputs08], [f(s16) for f in self.outputs16],
-                [f(s32) for f in self.outputs32]]
+        out = [[f(s08) for f in self.outputs08]]
+        if num_layers > 1:
+            s16 = self.layer4(s08)
+            out.append([f(s16) for f in self.outputs16])
+        if num_layers > 2:
+            out.append([f(self.layer5(s16)) for f in self.outputs32])
+        return out
 
 
 class BasicConv(nn.Module):
@@ -345,14 +349,16 @@ class UpdateHead(nn.Module):
 
 
 class BasicMultiUpdateBlock(nn.Module):
-    """Parameters of update.py:134-162 (predict_confidence=False, 3 GRU levels)."""
+    """Parameters of update.py:134-162 (predict_confidence=False).  All three GRUs exist at any
+    n_gru_layers, as in the reference; gru08 loses its interp(net[1]) input below 2 levels and
+    gru16 its interp(net[2]) input below 3 (update.py:149-150)."""
 
     def __init__(self, corr_levels=4, corr_radius=4, encoder_output_dim=128, hidden_dims=(128, 128, 128),
-                 n_downsample=2):
+                 n_downsample=2, n_gru_layers=3):
         super().__init__()
         self.encoder = BasicMotionEncoder(corr_levels, corr_radius)
-        self.gru08 = ConvGRU(hidden_dims[2], encoder_output_dim + hidden_dims[1])
-        self.gru16 = ConvGRU(hidden_dims[1], hidden_dims[0] + hidden_dims[2])
+        self.gru08 = ConvGRU(hidden_dims[2], encoder_output_dim + hidden_dims[1] * (n_gru_layers > 1))
+        self.gru16 = ConvGRU(hidden_dims[1], hidden_dims[0] * (n_gru_layers == 3) + hidden_dims[2])
         self.gru32 = ConvGRU(hidden_dims[0], hidden_dims[1])
         self.flow_head = UpdateHead(hidden_dims[2], 256, 2)
         f = 2 ** n_downsample

@@ -100,7 +100,7 @@ class HipCorrBlock1D:
                             out: torch.Tensor, other: Optional["HipCorrBlock1D"] = None):
         """Lookup of this pyramid (and ``other``'s) followed, in the same kernel, by a 1x1 conv
         + bias + ReLU of the taps -> out [B*nvol, Cout, H, W1] (sample b*nvol + v); on the
-        sheared copies when both blocks have one."""
+        sheared copies when both blocks have one.  num_levels 1..4, radius 1..8, Cout 64."""
         if self.sheared is not None and (other is None or other.sheared is not None):
             return ops.corr_lookup_conv1x1_sheared(self.sheared, None if other is None else other.sheared,
                                                    self.shape[3], self.num_levels, self.radius, coords_x, weight_kc,

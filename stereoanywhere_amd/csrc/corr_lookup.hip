@@ -12,6 +12,7 @@
 //   out = v[floor] * (1 - w) + v[floor + 1] * w, zero outside [0, W_l - 1].
 #include "sa_common.h"
 #include "convc1_mfma.h"
+#include "lookup_fold.h"
 
 namespace {
 
@@ -227,6 +228,29 @@ __global__ __launch_bounds__(256) void lookup_c1_vec_kernel(const float *__restr
   }
 }
 
+// Any other geometry (1..4 levels, radius 1..8): one thread per (volume, pixel) folds each tap into
+// its COUT accumulators as it is sampled (lookup_fold.h), reading the two cells of a tap from its
+// own pixel row; the output planes are written coalesced along the pixels.
+template <int COUT>
+__global__ __launch_bounds__(256) void lookup_c1_fold_kernel(const float *__restrict__ pa, const float *__restrict__ pb,
+                                                             const float *__restrict__ cx, LGeo g, long npix,
+                                                             const float *__restrict__ wt,
+                                                             const float *__restrict__ bias, int nvol,
+                                                             float *__restrict__ out) {
+  const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npix) return;
+  const int v = blockIdx.y;
+  const long hw = (long)g.H * g.W1;
+  const long b = p / hw, rem = p % hw;
+  const float x = cx[b * g.cbs + rem];
+  const float *__restrict__ row = (v ? pb : pa) + p * g.rs;
+  float acc[COUT];
+  sa::lookup_c1_fold<COUT>(x, g.L, g.r, g.wid, wt, bias, [&](int l, int k) { return row[g.off[l] + k]; }, acc);
+  float *__restrict__ o = out + (b * nvol + v) * COUT * hw + rem;
+#pragma unroll
+  for (int c = 0; c < COUT; ++c) o[(long)c * hw] = fmaxf(acc[c], 0.0f);
+}
+
 }  // namespace
 
 // convc1 of the fused lookups on the VALU (0, default) or on fp32 MFMA (1): the MFMA form measured
@@ -243,9 +267,9 @@ extern "C" int sa_corr_lookup_conv1x1(const float *pyramid_a, const float *pyram
                                       float *out, void *stream) {
   SA_REQUIRE(pyramid_a && coords_x && out && weight_kc && bias, "sa_corr_lookup_conv1x1: null pointer");
   SA_REQUIRE(B > 0 && H > 0 && W1 > 0 && W2 > 0, "sa_corr_lookup_conv1x1: empty shape");
-  SA_REQUIRE(num_levels == 4 && radius == 4 && Cout == 64,
-             "sa_corr_lookup_conv1x1: built for 4 levels, radius 4, 64 outputs (got %d, %d, %d)", num_levels, radius,
-             Cout);
+  SA_REQUIRE(num_levels >= 1 && num_levels <= 4 && radius >= 1 && radius <= 8 && Cout == 64,
+             "sa_corr_lookup_conv1x1: built for 1..4 levels, radius 1..8, 64 outputs (got %d, %d, %d)", num_levels,
+             radius, Cout);
   SA_REQUIRE(sa_pyramid_level_width(W2, num_levels - 1) >= 2,
              "sa_corr_lookup_conv1x1: level %d of width %d is too narrow to sample", num_levels - 1,
              sa_pyramid_level_width(W2, num_levels - 1));
@@ -266,6 +290,11 @@ extern "C" int sa_corr_lookup_conv1x1(const float *pyramid_a, const float *pyram
   hipStream_t s = sa::as_stream(stream);
   sa::TimingScope ts(SA_K_LOOKUP, s);
   dim3 grid((unsigned)((npix + 255) / 256), nvol);
+  if (num_levels != 4 || radius != 4) {   // the published (4, 4) keeps its own instances below
+    lookup_c1_fold_kernel<64><<<grid, 256, 0, s>>>(pyramid_a, pyramid_b ? pyramid_b : pyramid_a, coords_x, g, npix,
+                                                   weight_kc, bias, nvol, out);
+    return sa::check_launch("sa_corr_lookup_conv1x1");
+  }
   const long pyr_bytes = npix * row_stride * 4;
   if (pyr_bytes < (1L << 31) - 64 && row_stride % 4 == 0 && (long)H * W1 < (1L << 30)) {
     if (sa_lookup_mfma)

@@ -19,6 +19,7 @@
 // by sa_corr_pyramid_shear from the row-layout pyramid, read at every GRU iteration.
 #include "sa_common.h"
 #include "convc1_mfma.h"
+#include "lookup_fold.h"
 
 namespace {
 
@@ -280,6 +281,34 @@ __global__ __launch_bounds__(64 * NW) void lookup_c1_shear_lds_kernel(const floa
   }
 }
 
+// Any other geometry (1..4 levels, radius 1..8) on the sheared pyramid: lookup_c1_fold_kernel
+// (corr_lookup.hip) with the cells read from the rows e of column j; the same device function, so the
+// same bits as the row layout.  A cell k in [0, W_l) of pixel j sits at row e = (j >> l) - k + W_l - 1,
+// which lies in [0, E_l).
+template <int COUT>
+__global__ __launch_bounds__(256) void lookup_c1_shear_fold_kernel(const float *__restrict__ sa, const float *__restrict__ sb,
+                                                                   const float *__restrict__ cx, ShLGeo g, int L, int R,
+                                                                   int npix, const float *__restrict__ wt,
+                                                                   const float *__restrict__ bias, int nvol,
+                                                                   float *__restrict__ out) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= npix) return;
+  const int v = blockIdx.y;
+  const int hw = g.H * g.W1;
+  const int b = p / hw, rem = p - b * hw;
+  const int h = rem / g.W1, j = rem - h * g.W1;
+  const float x = cx[(long)b * g.cbs + rem];
+  const float *__restrict__ S = (v ? sb : sa) + ((long)b * g.H + h) * g.slice + j;
+  float acc[COUT];
+  sa::lookup_c1_fold<COUT>(x, L, R, g.wid, wt, bias, [&](int l, int k) {
+    const int e = (j >> l) - k + g.wid[l] - 1;
+    return S[g.off[l] + (long)e * g.P];
+  }, acc);
+  float *__restrict__ o = out + ((long)b * nvol + v) * COUT * hw + rem;
+#pragma unroll
+  for (int c = 0; c < COUT; ++c) o[(long)c * hw] = fmaxf(acc[c], 0.0f);
+}
+
 }  // namespace
 
 extern "C" int sa_lookup_get_mfma();
@@ -304,9 +333,9 @@ extern "C" long sa_shear_level_offset(int W1, int W2, int num_levels, int level)
 
 // 1 when the sheared pipeline (sa_corr_pyramid_shear + sa_corr_lookup_conv1x1_sheared) takes this
 // geometry: one grid z-slice per image row (B * H <= 65535), a 32-row LDS tile of the widest
-// level (W2 <= 511), a coarsest level of width >= 2 and a pixel count in int range
+// level (W2 <= 511), 1..4 levels with a coarsest level of width >= 2 and a pixel count in int range
 extern "C" int sa_corr_shear_supported(int B, int H, int W1, int W2, int num_levels) {
-  if (B <= 0 || H <= 0 || W1 <= 0 || W2 <= 0 || num_levels != 4) return 0;
+  if (B <= 0 || H <= 0 || W1 <= 0 || W2 <= 0 || num_levels < 1 || num_levels > 4) return 0;
   if ((long)B * H > 65535) return 0;
   if ((long)SH_J * (W2 + 1) * 4 > 64 * 1024) return 0;
   if (sa_pyramid_level_width(W2, num_levels - 1) < 2) return 0;
@@ -340,9 +369,9 @@ extern "C" int sa_corr_lookup_conv1x1_sheared(const float *sheared_a, const floa
                                               void *stream) {
   SA_REQUIRE(sheared_a && coords_x && out && weight_kc && bias, "sa_corr_lookup_conv1x1_sheared: null pointer");
   SA_REQUIRE(B > 0 && H > 0 && W1 > 0 && W2 > 0, "sa_corr_lookup_conv1x1_sheared: empty shape");
-  SA_REQUIRE(num_levels == 4 && radius == 4 && Cout == 64,
-             "sa_corr_lookup_conv1x1_sheared: built for 4 levels, radius 4, 64 outputs (got %d, %d, %d)", num_levels,
-             radius, Cout);
+  SA_REQUIRE(num_levels >= 1 && num_levels <= 4 && radius >= 1 && radius <= 8 && Cout == 64,
+             "sa_corr_lookup_conv1x1_sheared: built for 1..4 levels, radius 1..8, 64 outputs (got %d, %d, %d)",
+             num_levels, radius, Cout);
   SA_REQUIRE(sa_pyramid_level_width(W2, num_levels - 1) >= 2,
              "sa_corr_lookup_conv1x1_sheared: level %d of width %d is too narrow to sample", num_levels - 1,
              sa_pyramid_level_width(W2, num_levels - 1));
@@ -364,6 +393,11 @@ extern "C" int sa_corr_lookup_conv1x1_sheared(const float *sheared_a, const floa
   hipStream_t s = sa::as_stream(stream);
   sa::TimingScope ts(SA_K_LOOKUP, s);
   const float *sbb = sheared_b ? sheared_b : sheared_a;
+  if (num_levels != 4 || radius != 4) {   // the published (4, 4) keeps its own instances below
+    lookup_c1_shear_fold_kernel<64><<<dim3((unsigned)((npix + 255) / 256), nvol), 256, 0, s>>>(
+        sheared_a, sbb, coords_x, g, num_levels, radius, (int)npix, weight_kc, bias, nvol, out);
+    return sa::check_launch("sa_corr_lookup_conv1x1_sheared");
+  }
   if (g_shear_dual >= 2 && !sa_lookup_get_mfma()) {
     if (g_shear_dual == 3)
       lookup_c1_shear_lds_kernel<4, 4, 64, 8><<<(unsigned)((npix + 63) / 64), 512, 0, s>>>(

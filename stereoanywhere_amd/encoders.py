@@ -342,18 +342,19 @@ def fnet_forward(enc: nn.Module, x: torch.Tensor, table: Dict[str, ops.Affine],
 
 def cnet_forward(enc: nn.Module, x: torch.Tensor, table: Dict[str, ops.Affine],
                  wino: WinoTable = None, direct: DirectTable = None,
-                 fold: FoldTable = None) -> List[List[torch.Tensor]]:
+                 fold: FoldTable = None, num_layers: int = 3) -> List[List[torch.Tensor]]:
     """MultiBasicEncoder.forward (extractor.py:156-300) up to the head convs, whose outputs
-    are returned RAW (bias not added) as [[h08, c08], [h16, c16], [h32, c32]]; the caller
-    finishes them (tanh / relu with the bias) in one pass each."""
+    are returned RAW (bias not added) as [[h08, c08], [h16, c16], [h32, c32]][:num_layers]; the
+    caller finishes them (tanh / relu with the bias) in one pass each.  The stages and heads
+    past num_layers (the model's n_gru_layers) are not computed (extractor.py:288-295)."""
     _install(wino, direct, fold)
     fin = _Finisher("instance" if isinstance(enc.norm1, nn.InstanceNorm2d) else "batch", table)
     x = _stem(enc, x, fin)
     for s in ("layer1", "layer2", "layer3"):
         x = _stage(getattr(enc, s), s, x, fin)
     s08 = x
-    s16 = _stage(enc.layer4, "layer4", s08, fin)
-    s32 = _stage(enc.layer5, "layer5", s16, fin)
+    s16 = _stage(enc.layer4, "layer4", s08, fin) if num_layers > 1 else None
+    s32 = _stage(enc.layer5, "layer5", s16, fin) if num_layers > 2 else None
 
     def heads(seqs, name, feat):
         # the heads of one level (hidden state, context) read the same features: each of their
@@ -361,8 +362,12 @@ def cnet_forward(enc: nn.Module, x: torch.Tensor, table: Dict[str, ops.Affine],
         rs = residual_blocks_grouped([q[0] for q in seqs], [f"{name}.{i}.0" for i in range(len(seqs))],
                                      [feat] * len(seqs), fin)
         return _convs_grouped([q[1] for q in seqs], rs)
-    return [heads(enc.outputs08, "outputs08", s08), heads(enc.outputs16, "outputs16", s16),
-            _convs_grouped(list(enc.outputs32), [s32] * len(enc.outputs32))]
+    out = [heads(enc.outputs08, "outputs08", s08)]
+    if num_layers > 1:
+        out.append(heads(enc.outputs16, "outputs16", s16))
+    if num_layers > 2:
+        out.append(_convs_grouped(list(enc.outputs32), [s32] * len(enc.outputs32)))
+    return out
 
 
 def fold_table(enc: nn.Module) -> FoldTable:

@@ -25,6 +25,10 @@ classifier outputs trilinearly back to 1/4) and use_aggregate_stereo_vol (the ma
 volume through hourglass_stereo + classifier_stereo, times the truncation volume, as the
 stereo pyramid); n_additional_hourglass > 1 takes the unfused hourglass.  Combinations the
 reference cannot run either raise (tests/golden/flags.npz).
+Geometry: n_gru_layers 1..3, corr_levels 1..4 and corr_radius 1..8 at n_downsample = 2 (the
+published 3 / 4 / 4 on its own lookup kernels, every other pair on csrc/lookup_fold.h);
+corr_levels > 4 and n_downsample = 1 raise NotImplementedError at construction, n_downsample = 3
+(where the reference raises IndexError, tests/golden/geometry.npz) from forward.
 """
 from __future__ import annotations
 
@@ -139,6 +143,19 @@ class StereoAnywhere(nn.Module):
                 setattr(args, k, v)
         self.args = args
         a = args
+        # the geometry grid this build runs: refused here, where the reason is visible,
+        # not from a kernel's argument check deep in the GRU loop
+        if a.n_downsample == 1:
+            # (the reference runs it; at 3 its own forward raises IndexError, tests/golden/geometry.npz,
+            # and forward() here refuses it as before)
+            raise NotImplementedError("n_downsample=1: only n_downsample=2 (the 1/4 grid) is built")
+        if a.n_gru_layers not in (1, 2, 3):
+            raise NotImplementedError(f"n_gru_layers={a.n_gru_layers}: 1, 2 or 3 GRU levels are supported")
+        if not 1 <= a.corr_levels <= 4:
+            raise NotImplementedError(f"corr_levels={a.corr_levels}: 1..4 pyramid levels are supported (the pyramid's "
+                                      "row layout holds four)")
+        if not 1 <= a.corr_radius <= 8:
+            raise NotImplementedError(f"corr_radius={a.corr_radius}: the fused lookup takes radius 1..8")
         self.cnet = MultiBasicEncoder(output_dim=[a.context_dims, a.context_dims], norm_fn="batch",
                                       downsample=a.n_downsample)
         self.context_zqr_convs = nn.ModuleList(
@@ -158,7 +175,7 @@ class StereoAnywhere(nn.Module):
         self.classifier_mono = nn.Conv3d(a.volume_channels, 1, 3, 1, 1, bias=False)
         self.classifier_monoconf = nn.Conv3d(a.volume_channels, 1, 3, 1, 1, bias=False)
         self.update_block = BasicMultiUpdateBlock(a.corr_levels, a.corr_radius, a.encoder_output_dim,
-                                                  a.context_dims, a.n_downsample)
+                                                  a.context_dims, a.n_downsample, a.n_gru_layers)
         self._derived = None
         self._derived_key = None
         # side streams before the update loop (_forward); False runs everything on the
@@ -190,10 +207,13 @@ class StereoAnywhere(nn.Module):
         if self._derived_key != key:
             ub = self.update_block
             hd = self.args.context_dims
+            n = self.args.n_gru_layers
+            # the GRUs that run (update.py:166-183): gru08 always, gru16 from 2 levels, gru32 at 3;
+            # each split follows its GRU's own input width (_split_gru cuts at the hidden width)
+            grus = [("g08", ub.gru08, hd[2]), ("g16", ub.gru16, hd[1]), ("g32", ub.gru32, hd[0])][:n]
             with torch.no_grad():
                 self._derived = dict(
-                    g08=self._split_gru(ub.gru08, hd[2]), g16=self._split_gru(ub.gru16, hd[1]),
-                    g32=self._split_gru(ub.gru32, hd[0]),
+                    **{gk: self._split_gru(gru, h) for gk, gru, h in grus},
                     # reference conv over (H, W1, W2) == conv over (W2, H, W1) with permuted kernel
                     cls_d=self.classifier_mono.weight.permute(0, 1, 4, 2, 3).contiguous(),
                     cls_c=self.classifier_monoconf.weight.permute(0, 1, 4, 2, 3).contiguous(),
@@ -211,7 +231,7 @@ class StereoAnywhere(nn.Module):
                     bn_cnet=encoders.bn_table(self.cnet), bn_fnet=encoders.bn_table(self.fnet),
                     head_b=[(self.cnet.outputs08[0][1].bias, self.cnet.outputs08[1][1].bias),
                             (self.cnet.outputs16[0][1].bias, self.cnet.outputs16[1][1].bias),
-                            (self.cnet.outputs32[0].bias, self.cnet.outputs32[1].bias)],
+                            (self.cnet.outputs32[0].bias, self.cnet.outputs32[1].bias)][:n],
                 )
                 # Winograd F(2x2,3x3) filters (ops.conv2d_k3) of every eligible 3x3 conv
                 d = self._derived
@@ -221,7 +241,7 @@ class StereoAnywhere(nn.Module):
                 # the stems and the stride-2 blocks on the direct fp32-MFMA conv (ops.conv_direct)
                 # (opts.direct_conv = False leaves them on MIOpen)
                 d["direct"] = encoders.direct_table(self.cnet, self.fnet) if self.opts.direct_conv else {}
-                for gk in ("g08", "g16", "g32"):
+                for gk, _, _ in grus:
                     g = d[gk]
                     half = g["wqh"].shape[1] // 2
                     g.update(Ux=ops.wino_weights(g["wx"]), Uhzr=ops.wino_weights(g["whzr"]),
@@ -261,8 +281,8 @@ class StereoAnywhere(nn.Module):
         a = self.args
         if not test_mode:
             raise NotImplementedError("training forward (test_mode=False) is outside the inference tier")
-        if a.n_gru_layers != 3 or a.n_downsample != 2:
-            raise NotImplementedError("only 3 GRU levels at n_downsample=2 are built")
+        if a.n_downsample != 2:
+            raise NotImplementedError(f"n_downsample={a.n_downsample}: only n_downsample=2 (the 1/4 grid) is built")
         if a.vol_downsample > 0 and (a.use_aggregate_stereo_vol or not a.use_aggregate_mono_vol):
             # the reference fails on these combinations too (tests/golden/flags.npz): its
             # full-resolution stereo volume meets the downsampled masks, or its GRU samples the
@@ -323,7 +343,7 @@ class StereoAnywhere(nn.Module):
         # ---- context + feature encoders: 3x3 convs on the HIP Winograd / implicit-GEMM kernels,
         # stems and stride-2 convs on the direct kernel, epilogues fused (encoders.py)
         if self.cnet.training or self.fnet.training:  # batch-statistics BatchNorm: module path
-            cl = self.cnet(mde2.repeat(1, 3, 1, 1))
+            cl = self.cnet(mde2.repeat(1, 3, 1, 1), num_layers=a.n_gru_layers)
             hid = [torch.tanh(x[0]).contiguous() for x in cl]
             ctx = [conv(torch.relu(x[1])) for x, conv in zip(cl, self.context_zqr_convs)]
             fm = self.fnet(torch.cat([image2, image3], 0))
@@ -357,10 +377,12 @@ class StereoAnywhere(nn.Module):
         # ---- pyramids
         trunc = (sm2, mirror) if a.use_truncate_vol else (None, None)
         # the sheared lookup for large volumes, where its kernels take the geometry (W4 <= 511,
-        # B * H4 <= 65535 image rows, 4 levels of radius 4); the row layout otherwise
+        # B * H4 <= 65535 image rows); the row layout otherwise
         big = (self.opts.sheared_lookup and B * H4 * W4 * W4 * 4 >= self.opts.shear_min_bytes
-               and a.corr_levels == 4 and a.corr_radius == 4 and ops.shear_supported(B, H4, W4, W4, a.corr_levels))
-        direct = self.opts.sheared_producers and big
+               and ops.shear_supported(B, H4, W4, W4, a.corr_levels))
+        # (the producers that write the sheared layout themselves are exercised at 4 levels only:
+        # any other level count takes the row pyramid and the copy pass below)
+        direct = self.opts.sheared_producers and big and a.corr_levels == 4
         if a.use_aggregate_stereo_vol:
             stereo_blk = self._stereo_aggregate(dw, fmap2, fmap3, mde2, mde3, m2l, m3l, trunc, B, H4, W4)
         else:
@@ -457,12 +479,12 @@ class StereoAnywhere(nn.Module):
         """Context encoder (eval BatchNorm folded) -> tanh hidden states and the context_zqr
         convs (stereoanywhere.py:116-121)."""
         cl = encoders.cnet_forward(self.cnet, mde2.repeat(1, 3, 1, 1), dw["bn_cnet"], dw["wino"], dw["direct"],
-                                   dw["fold_cnet"])
+                                   dw["fold_cnet"], num_layers=self.args.n_gru_layers)
         hid, cs = [], []
         for (h_raw, c_raw), (hb, cb) in zip(cl, dw["head_b"]):
             hid.append(ops.norm_act(h_raw, ops.Affine(t=hb), act_in="tanh", out=h_raw))
             cs.append(ops.norm_act(c_raw, ops.Affine(t=cb), act_in="relu", out=c_raw))
-        # the three context_zqr convs ([B,384,..] per level) in one launch
+        # the context_zqr convs of the levels that exist ([B,384,..] per level) in one launch
         ctx = ops.conv2d_k3_multi(*[dict(x=c, U=U, bias=conv.bias)
                                     for c, U, conv in zip(cs, dw["U_ctx"], self.context_zqr_convs)])
         return hid, ctx
@@ -605,22 +627,26 @@ class StereoAnywhere(nn.Module):
                               _shape=(B, H4, W4, W4))
 
     def _iterate(self, dw, hid, ctx, stereo_blk, mono_blk, coords_x, iters, B, H4, W4):
-        """The GRU loop as a generator: it yields twice per iteration (after gru16 and at the
-        end) so that batch parts on separate streams can be enqueued in turn (_iterate_parts);
+        """The GRU loop as a generator: it yields twice per iteration (after gru16, or after the
+        motion encoder where there is no gru16, and at the end) so that batch parts on separate
+        streams can be enqueued in turn (_iterate_parts);
         its return value is (flow_up, None)."""
         ub = self.update_block
         enc = ub.encoder
         dev = coords_x.device
         f32 = torch.float32
-        h08, h16, h32 = hid
-        H8, W8 = h16.shape[2:]
-        H16, W16 = h32.shape[2:]
+        # the GRU levels that run (n_gru_layers of them): "08" at 1/4, "16" at 1/8, "32" at 1/16
+        n = len(hid)
+        keys = ("08", "16", "32")[:n]
+        h08 = hid[0]
         c1 = torch.empty((2 * B, enc.convc1.out_channels, H4, W4), device=dev, dtype=f32)  # convc1(lookups)
         motin = torch.empty((B, 192, H4, W4), device=dev, dtype=f32)  # [convc2 stereo | mono | convf2]
         flow = torch.empty((B, 2, H4, W4), device=dev, dtype=f32)
-        # x08 = [motion(126) | flow(2) | interp(h16)], x16 = [pool(h08) | interp(h32)], x32 = [pool(h16)]
-        xdims = {"08": 256, "16": 256, "32": 128}
-        shapes = {"08": (H4, W4), "16": (H8, W8), "32": (H16, W16)}
+        # x08 = [motion(126) | flow(2) | interp(h16)], x16 = [pool(h08) | interp(h32)], x32 = [pool(h16)];
+        # the interp part is there only when the coarser level runs (update.py:149-150, 169-183)
+        xdims = {"08": 128 + (128 if n > 1 else 0), "16": 128 + (128 if n > 2 else 0), "32": 128}
+        xdims = {k: xdims[k] for k in keys}
+        shapes = {k: tuple(h.shape[2:]) for k, h in zip(keys, hid)}
         lvl_of = {"08": 0, "16": 1, "32": 2}
         hd = h08.shape[1]
         o = self.opts
@@ -642,7 +668,7 @@ class StereoAnywhere(nn.Module):
         fuse_out = {k: fused[k] and (o.fuse_out or wid[k] is not None) for k in shapes}
         hxr, xq, rh, xs = {}, {}, {}, {}
         ctxp = list(ctx)
-        for k, h in zip(("08", "16", "32"), hid):
+        for k, h in zip(keys, hid):
             if fused[k]:
                 padded = wid[k] is not None
                 alloc = torch.zeros if padded else torch.empty
@@ -664,9 +690,9 @@ class StereoAnywhere(nn.Module):
                 xs[k] = torch.empty((B, xdims[k], *shapes[k]), device=dev, dtype=f32)
                 rh[k] = torch.empty_like(h)
         ctx = ctxp
-        h08, h16, h32 = (hxr[k][:, :hd] if fused[k] else h for k, h in zip(("08", "16", "32"), hid))
-        x08, x16, x32 = xs["08"], xs["16"], xs["32"]
-        hs = {"08": h08, "16": h16, "32": h32}
+        hs = {k: hxr[k][:, :hd] if fused[k] else h for k, h in zip(keys, hid)}
+        h08, h16, h32 = (hs.get(k) for k in ("08", "16", "32"))
+        x08, x16, x32 = (xs.get(k) for k in ("08", "16", "32"))
         z = {k: (torch.zeros if wid[k] is not None else torch.empty)(h.shape, device=dev, dtype=f32)
              for k, h in hs.items()}
         cz = [c[:, 0:128] for c in ctx]
@@ -732,56 +758,68 @@ class StereoAnywhere(nn.Module):
         def pool(src, ks, dst, kd):
             ops.pool2x(src, dst, width=wid[ks], out_width=wid[kd])
 
-        pool(h16, "16", x32, "32")
-        xc32, hzr32 = conv_group(*gate_x_h("32", x32, h32), name="pro32")
-        gru_zr(2, "32", h32, xc32, hzr32)
-        q_finish(2, "32", xc32, conv_group(*q_probs("32", False), name="pro32"))
+        # Below 3 levels there is no gru32, so no prologue and nothing carried over; at 1 level the
+        # motion encoder's convs have launches of their own and no pool / interp job runs.
+        if n == 3:
+            pool(h16, "16", x32, "32")
+            xc32, hzr32 = conv_group(*gate_x_h("32", x32, h32), name="pro32")
+            gru_zr(2, "32", h32, xc32, hzr32)
+            q_finish(2, "32", xc32, conv_group(*q_probs("32", False), name="pro32"))
         for it in range(iters):
             last = it == iters - 1
+            ahead = n == 3 and not last   # gru32 of the next iteration in this one's launches
             # lookup of both pyramids + convc1 + ReLU in one kernel (sample 2b: stereo, 2b+1: mono)
             stereo_blk.lookup_conv1x1_into(coords_x, dw["c1_kc"], enc.convc1.bias, c1, other=mono_blk)
             # (the flow's vertical channel is identically zero, written so by flow_update: convf1
             # over channel 0 alone adds the same products, without the 49 zero taps)
             fl = ops.conv2d_small(flow[:, :1], dw["f1"], enc.convf1.bias, 64, 7, relu=True)
             # pool2x(h08) and interp(h32) into gru16's input, one launch
-            ops.resample_multi(("pool", h08, x16[:, :128], wid["08"], wid["16"]),
-                               ("interp", h32, x16[:, 128:], wid["32"], wid["16"]))
+            if n == 3:
+                ops.resample_multi(("pool", h08, x16[:, :128], wid["08"], wid["16"]),
+                                   ("interp", h32, x16[:, 128:], wid["32"], wid["16"]))
+            elif n == 2:   # (update.py:172: pool2x(net[0]) alone)
+                ops.resample_multi(("pool", h08, x16, wid["08"], wid["16"]))
             # gru16's x/h convs + the motion encoder's 3x3 convs (bias + ReLU in the epilogue,
             # written straight into the motion conv's input cat(convc2(stereo), convc2(mono),
             # convf2(convf1(flow))))
             mconv = [dict(x=c1v[:, v], U=dw["U_c2"], bias=enc.convc2.bias, relu=True,
                           out=motin[:, 64 * v:64 * v + 64]) for v in range(2)]
             mconv.append(dict(x=fl, U=dw["U_f2"], bias=enc.convf2.bias, relu=True, out=motin[:, 128:192]))
-            xc16, hzr16 = conv_group(*gate_x_h("16", x16, h16), *mconv, name="zr16")[:2]
-            gru_zr(1, "16", h16, xc16, hzr16)
-            # gru16's r*h conv + the motion conv (_conv: 126 outputs, padded to 128, into
-            # x08[:, :128]; channels 126-127 (the flow) are rewritten right after)
-            qp = q_probs("16", False)
-            res = conv_group(*qp, dict(x=motin, U=dw["U_mot"], bias=dw["mot_b"], relu=True, out=x08[:, :128]),
-                             name="q16")
-            q_finish(1, "16", xc16, res[:len(qp)])
+            # the motion conv (_conv: 126 outputs, padded to 128, into x08[:, :128]; channels
+            # 126-127 (the flow) are rewritten right after)
+            mot = dict(x=motin, U=dw["U_mot"], bias=dw["mot_b"], relu=True, out=x08[:, :128])
+            if n > 1:
+                xc16, hzr16 = conv_group(*gate_x_h("16", x16, h16), *mconv, name="zr16")[:2]
+                gru_zr(1, "16", h16, xc16, hzr16)
+                # gru16's r*h conv + the motion conv
+                qp = q_probs("16", False)
+                res = conv_group(*qp, mot, name="q16")
+                q_finish(1, "16", xc16, res[:len(qp)])
+            else:
+                conv_group(*mconv, name="zr16")
+                conv_group(mot, name="q16")
             yield   # half an iteration (the batch-parts schedule interleaves here)
             # the flow planes of x08 (after the motion conv wrote its padding channels there),
             # interp(h16) into gru08's input and (not last) pool2x(h16) into gru32's, one launch
             ops.resample_multi(("flow_x", coords_x, x08[:, 126:128], None, None),
-                               ("interp", h16, x08[:, 128:], wid["16"], wid["08"]),
-                               *([] if last else [("pool", h16, x32, wid["16"], wid["32"])]))
+                               *([("interp", h16, x08[:, 128:], wid["16"], wid["08"])] if n > 1 else []),
+                               *([("pool", h16, x32, wid["16"], wid["32"])] if ahead else []))
             # gru08's x/h convs (+ gru32's of the next iteration), then the r*h convs
             probs = gate_x_h("08", x08, h08)
-            if not last:
+            if ahead:
                 probs += gate_x_h("32", x32, h32)
             res = conv_group(*probs, name="zr08")
             xc08, hzr08 = res[:2]
             gru_zr(0, "08", h08, xc08, hzr08)
             qp = q_probs("08", True)
             probs = list(qp)
-            if not last:
+            if ahead:
                 xc32, hzr32 = res[2:]
                 gru_zr(2, "32", h32, xc32, hzr32)
                 probs += q_probs("32", True)
             qh = conv_group(*probs, name="q08")
             q_finish(0, "08", xc08, qh[:len(qp)])
-            if not last:
+            if ahead:
                 q_finish(2, "32", xc32, qh[len(qp):])
             # flow head + coordinate update (update.py:98-110, stereoanywhere.py:283-285); fused: conv1's
             # epilogue sums conv2's channel-0 taps, so conv1's 256-channel output is never written

@@ -204,11 +204,19 @@ def corr_lookup(pyr_a: torch.Tensor, pyr_b: Optional[torch.Tensor], W2: int, num
     return out
 
 
+def _lookup_bytes(npix: int, nvol: int, num_levels: int, radius: int, cout: int) -> float:
+    """Algorithmic bytes of one fused lookup: per pixel the coordinate, per volume the 2r + 2 cells
+    of each level's window and the cout output planes."""
+    return 4.0 * npix * (1 + nvol * (num_levels * (2 * radius + 2) + cout))
+
+
 def corr_lookup_conv1x1(pyr_a: torch.Tensor, pyr_b: Optional[torch.Tensor], W2: int, num_levels: int, radius: int,
                         coords_x: torch.Tensor, weight_kc: torch.Tensor, bias: torch.Tensor,
                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Lookup fused with a 1x1 conv + bias + ReLU of the taps (the motion encoder's convc1):
-    weight_kc [L*(2r+1), Cout] -> out [B*nvol, Cout, H, W1], sample b*nvol + v."""
+    weight_kc [L*(2r+1), Cout] -> out [B*nvol, Cout, H, W1], sample b*nvol + v.  1..4 levels,
+    radius 1..8, Cout 64: (4, 4) on its own kernel instances, every other pair on the
+    tap-folding kernel (csrc/lookup_fold.h); the library refuses anything else."""
     _check(pyr_a, "pyramid_a")
     if pyr_b is not None:
         _check(pyr_b, "pyramid_b")
@@ -224,18 +232,22 @@ def corr_lookup_conv1x1(pyr_a: torch.Tensor, pyr_b: Optional[torch.Tensor], W2: 
     Cout = weight_kc.shape[1]
     if weight_kc.shape[0] != num_levels * (2 * radius + 1):
         raise RuntimeError("weight_kc must be [L*(2r+1), Cout]")
+    if bias.numel() != Cout:
+        raise RuntimeError("bias must be [Cout]")
     if out is None:
         out = torch.empty((B * nvol, Cout, H, W1), device=pyr_a.device, dtype=torch.float32)
     _check(out, "out")
     N.call("sa_corr_lookup_conv1x1", pyr_a.data_ptr(), _ptr(pyr_b), W2, pyr_a.shape[1], num_levels, radius,
            coords_x.data_ptr(), cbs, B, H, W1, weight_kc.data_ptr(), bias.data_ptr(), Cout, out.data_ptr(),
            _stream(pyr_a))
+    _account("corr_lookup", _lookup_bytes(B * H * W1, nvol, num_levels, radius, Cout))
     return out
 
 
 def shear_supported(B: int, H: int, W1: int, W2: int, num_levels: int = 4) -> bool:
     """Whether the sheared lookup pipeline takes this geometry (sa_corr_shear_supported: B*H <=
-    65535 image rows, W2 <= 511 for the shear pass's LDS tile, 4 levels); else the row layout."""
+    65535 image rows, W2 <= 511 for the shear pass's LDS tile, 1..4 levels with the coarsest at
+    least 2 wide); else the row layout."""
     return bool(N.lib().sa_corr_shear_supported(B, H, W1, W2, num_levels))
 
 
@@ -255,7 +267,8 @@ def corr_pyramid_shear(pyr: torch.Tensor, B: int, H: int, W1: int, W2: int, num_
 def corr_lookup_conv1x1_sheared(sh_a: torch.Tensor, sh_b: Optional[torch.Tensor], W2: int, num_levels: int,
                                 radius: int, coords_x: torch.Tensor, weight_kc: torch.Tensor, bias: torch.Tensor,
                                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """corr_lookup_conv1x1 on sheared pyramids [B*H, slice] (corr_pyramid_shear)."""
+    """corr_lookup_conv1x1 on sheared pyramids [B*H, slice] (corr_pyramid_shear): the same levels
+    and radii, and the same bits as the row layout gives from the same cells."""
     _check(sh_a, "sheared_a")
     if sh_b is not None:
         _check(sh_b, "sheared_b")
@@ -275,6 +288,7 @@ def corr_lookup_conv1x1_sheared(sh_a: torch.Tensor, sh_b: Optional[torch.Tensor]
     N.call("sa_corr_lookup_conv1x1_sheared", sh_a.data_ptr(), _ptr(sh_b), W2, num_levels, radius,
            coords_x.data_ptr(), cbs, B, H, W1, weight_kc.data_ptr(), bias.data_ptr(), Cout, out.data_ptr(),
            _stream(sh_a))
+    _account("corr_lookup", _lookup_bytes(B * H * W1, nvol, num_levels, radius, Cout))
     return out
 
 
