@@ -29,11 +29,12 @@ extern "C" {
  * that sa_abi_version() == SA_ABI_VERSION and that sa_struct_size(SA_STRUCT_*) equals its own
  * sizeof: the arrays of SaWinoProblem / SaGateEpilogue / SaResampleJob are read at the library's
  * stride, so a host built against another layout would hand over misread fields.
+ *   8: block_shape 7 of sa_conv2d_k3_wino4_multi_gate / sa_conv2d_k3_wino4_launch (additive)
  *   7: sa_feature_gates / SaFeatureGateJob added (additive: no earlier entry point changed)
  *   6: round 6 (the implicit-GEMM entry points removed; sa_struct_size, sa_conv3d_mf_get_planes)
  *   5: SaWinoProblem gained the residual-epilogue fields (skip ... out_act); sa_conv2d_k3_wino4_launch
  *      took a guard flag; sa_conv2d_wino4_weights_cb removed */
-#define SA_ABI_VERSION 7
+#define SA_ABI_VERSION 8
 enum { SA_STRUCT_WINO_PROBLEM = 0, SA_STRUCT_GATE_EPILOGUE = 1, SA_STRUCT_RESAMPLE_JOB = 2, SA_STRUCT_FEATURE_GATE_JOB = 3 };
 int sa_abi_version(void);
 /* sizeof the struct `which` (SA_STRUCT_*) as the library was built, -1 for an unknown id */
@@ -529,14 +530,18 @@ typedef struct SaGateEpilogue {
  * waves, 32 tiles, two per CU: shorter launches of few rounds fill the chip better), 6 split large
  * blocks (8 waves, 64 tiles x 32 output channels; every problem's U from
  * sa_conv2d_wino4_weights_split; the transformed inputs must stay below 65504 in magnitude, see the
- * guard of sa_conv2d_k3_wino4_launch).  Any other value is an error. */
+ * guard of sa_conv2d_k3_wino4_launch), 7 the mixed-precision form of 6: the same filter buffer, guard
+ * flag and preconditions, but each Winograd-domain input is a single f16, hi = f16(V) (relative
+ * rounding 2^-11 per value), against the exact (hi, lo) filter pairs, fp32 accumulation; every
+ * tensor in memory stays fp32.  Any other value is an error. */
 int sa_conv2d_k3_wino4_multi_gate(int nprob, const SaWinoProblem *probs, const SaGateEpilogue *gates,
                                   int block_shape, void *stream);
 /* sa_conv2d_k3_wino4_multi_gate with the split kernel's range guard (block_shape 6, guard != 0): a
  * block whose f16 operands overflowed (|transformed input| >= 65520, or an input not finite) writes
  * nothing and recomputes its work item right away on fp32 MFMA products (the split filters read as
  * hi + lo), so results never carry the overflow; every such block in parallel, no second launch.
- * sa_split_redo_blocks counts them.  Other block shapes ignore guard. */
+ * sa_split_redo_blocks counts them.  block_shape 7 takes the guard the same way (its second pass
+ * runs the same single-f16 products on the scaled inputs).  Other block shapes ignore guard. */
 int sa_conv2d_k3_wino4_launch(int nprob, const SaWinoProblem *probs, const SaGateEpilogue *gates,
                               int block_shape, int guard, void *stream);
 /* Blocks of the split kernels (F(4x4) and sa_conv_direct_split) that the range

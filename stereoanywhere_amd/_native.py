@@ -207,7 +207,7 @@ def lib() -> ctypes.CDLL:
 
 # include/stereoanywhere_hip.h SA_ABI_VERSION: the library must be built from the same header as
 # these bindings (the struct arrays are read at the library's stride)
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 def _check_abi(h) -> None:

@@ -51,6 +51,11 @@
 // 58.7 -> 58.1 ms/step, two interleaved passes (profiles/ab/r06_w4_pair_ab.txt)
 #define SA_W4_PAIR_AFF 1
 #endif
+#ifndef SA_W4_PAIR_AFF_HALF
+// the half (mixed-precision) kernel with the affine input stays on the unpaired loop: paired it
+// spills the same 28 B per lane, and the new instances get no spill allowance
+#define SA_W4_PAIR_AFF_HALF 0
+#endif
 #ifndef SA_W4_GJB
 #define SA_W4_GJB 4    // gate-epilogue store iterations whose plane loads go out together (mode 2)
 #endif
@@ -119,6 +124,21 @@ using W4Small = W4Cfg<4, 4>;
 // at most 100-fold over the input patch.
 using W4Split = W4Cfg<8, 8, true>;
 constexpr int W4S_LOG2 = 12;
+// Half (block_shape 7, the mixed-precision mode): the split kernel with the Winograd-domain input
+// as ONE f16, hi = f16(V) (relative rounding 2^-11 per transformed value); the lo half, its two
+// converts, its v_fma_mix and its MFMA per (row, group) are gone.  The filters stay the exact
+// (bhi, blo) pairs of the same LDS image: the paired A operand (hi0, hi0, hi1, hi1) against
+// B = (bhi0, blo0, bhi1, blo1) gives hi0 (bhi0 + blo0) + hi1 (bhi1 + blo1) in fp32.  Scaling, range
+// guard (an overflowed hi is +-inf: the staged sums turn non-finite), output transform and
+// epilogues are the split kernel's.  A config type of its own, not a W4Cfg parameter: the split
+// instances keep their names.
+struct W4Half : W4Cfg<8, 8, true> {
+  static constexpr bool HALF = true;
+};
+template <class C, class = void>
+struct W4IsHalf : std::false_type {};
+template <class C>
+struct W4IsHalf<C, std::enable_if_t<C::HALF>> : std::true_type {};
 static_assert(2 * W4Small::SMEM * 4 <= 160 * 1024, "two small blocks per CU");
 
 struct W4Prob {
@@ -208,6 +228,13 @@ __device__ __forceinline__ void w4_pair_split(const float x0, const float x1, f1
   const f16x2 q1 = __builtin_convertvector(f32x2{l1, 0.0f}, f16x2);
   ahi = __builtin_shufflevector(h0, h1, 0, 1, 2, 3);
   alo = __builtin_shufflevector(q0, q1, 0, 1, 2, 3);
+}
+
+// The half kernel's A operand of a lane's two channels: (hi0, hi0, hi1, hi1), round-to-nearest-even
+__device__ __forceinline__ f16x4 w4_pair_half(const float x0, const float x1) {
+  const f16x2 h0 = __builtin_convertvector(f32x2{x0, x0}, f16x2);
+  const f16x2 h1 = __builtin_convertvector(f32x2{x1, x1}, f16x2);
+  return __builtin_shufflevector(h0, h1, 0, 1, 2, 3);
 }
 
 // Range guard of the split kernel: blocks whose f16 operands overflowed (|V| >= 65520 turns hi
@@ -549,7 +576,7 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
   constexpr int NWAVE = C::NW, NTHR = C::NTHR, KC = C::KC, JPC = C::JPC, NT = C::NT, PDMA = C::PDMA,
                 UDMA = C::UDMA, UPW = C::UPW, UBUF = C::UBUF, BUF = C::BUF, PBUF = C::PBUF, OPP = C::OPP,
                 CO = C::CO, CG = C::CG, SB = C::SB, NR = C::NR;
-  constexpr bool SPLIT = C::SPLIT;
+  constexpr bool SPLIT = C::SPLIT, HALF = W4IsHalf<C>::value;
   static_assert(!SPLIT || NWAVE == 8, "split: the 8-wave shape");
   // a lane's filter operands of a point: one float, or (split) one f16 (hi, lo) pair, per group
   using f32xg = float __attribute__((ext_vector_type(CG)));
@@ -810,7 +837,7 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
         }
       }
     };
-    if constexpr (SPLIT && SA_W4_PAIR != 0 && JPC == 2 && (!AFF || SA_W4_PAIR_AFF)) {
+    if constexpr (SPLIT && SA_W4_PAIR != 0 && JPC == 2 && (!AFF || (HALF ? SA_W4_PAIR_AFF_HALF : SA_W4_PAIR_AFF))) {
       // both jobs' row passes first, then per column both jobs' column passes feed one MFMA pair per
       // (row, output-channel group) (w4_pair_split); a column's filter operands are read under its
       // two column passes
@@ -840,13 +867,22 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
           if (i == 1) load_bp(jj, NR / 2, NR, pc_);
-          f16x4 ahi, alo;
-          w4_pair_split(v0[i], v1[i], ahi, alo);
+          if constexpr (HALF) {   // one f16 per value: one MFMA per (row, group)
+            const f16x4 ahi = w4_pair_half(v0[i], v1[i]);
 #pragma unroll
-          for (int g = 0; g < CG; ++g) {
-            const f16x4 bp = __builtin_bit_cast(f16x4, g == 0 ? pc_[i].xy : pc_[i].zw);
-            acc[i][jj][g] = __builtin_amdgcn_mfma_f32_16x16x16f16(ahi, bp, acc[i][jj][g], 0, 0, 0);
-            acc[i][jj][g] = __builtin_amdgcn_mfma_f32_16x16x16f16(alo, bp, acc[i][jj][g], 0, 0, 0);
+            for (int g = 0; g < CG; ++g) {
+              const f16x4 bp = __builtin_bit_cast(f16x4, g == 0 ? pc_[i].xy : pc_[i].zw);
+              acc[i][jj][g] = __builtin_amdgcn_mfma_f32_16x16x16f16(ahi, bp, acc[i][jj][g], 0, 0, 0);
+            }
+          } else {
+            f16x4 ahi, alo;
+            w4_pair_split(v0[i], v1[i], ahi, alo);
+#pragma unroll
+            for (int g = 0; g < CG; ++g) {
+              const f16x4 bp = __builtin_bit_cast(f16x4, g == 0 ? pc_[i].xy : pc_[i].zw);
+              acc[i][jj][g] = __builtin_amdgcn_mfma_f32_16x16x16f16(ahi, bp, acc[i][jj][g], 0, 0, 0);
+              acc[i][jj][g] = __builtin_amdgcn_mfma_f32_16x16x16f16(alo, bp, acc[i][jj][g], 0, 0, 0);
+            }
           }
         }
         __builtin_amdgcn_sched_barrier(0);   // bound the scheduler's hoisting (register pressure)
@@ -888,7 +924,10 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
         if constexpr (SPLIT) {
 #pragma unroll
           for (int i = 0; i < NR; ++i) {
-            const f16x4 a = w4_split(v[i]);
+            // (half: (hi, hi, 0, 0) against the duplicated (bhi, blo) dword)
+            const f16x4 a = HALF ? __builtin_shufflevector(__builtin_convertvector(f32x2{v[i], v[i]}, f16x2),
+                                                           f16x2{(_Float16)0.0f, (_Float16)0.0f}, 0, 1, 2, 3)
+                                 : w4_split(v[i]);
             const f16x4 b0 = __builtin_bit_cast(f16x4, f32x2{bc[i][0], bc[i][0]});
             const f16x4 b1 = __builtin_bit_cast(f16x4, f32x2{bc[i][1], bc[i][1]});
             acc[i][jj][0] = __builtin_amdgcn_mfma_f32_16x16x16f16(a, b0, acc[i][jj][0], 0, 0, 0);
@@ -1300,13 +1339,14 @@ extern "C" int sa_conv2d_k3_wino4_multi_gate(int nprob, const SaWinoProblem *pro
 extern "C" int sa_conv2d_k3_wino4_launch(int nprob, const SaWinoProblem *probs, const SaGateEpilogue *gates,
                                          int block_shape, int guard, void *stream) {
   SA_REQUIRE(nprob >= 1 && nprob <= MAX_PROB && probs, "sa_conv2d_k3_wino4_multi: 1..%d problems", MAX_PROB);
-  SA_REQUIRE(block_shape == 0 || block_shape == 1 || block_shape == 2 || block_shape == 6,
-             "sa_conv2d_k3_wino4_multi: block_shape 0, 1, 2 or 6 (got %d)", block_shape);
+  SA_REQUIRE(block_shape == 0 || block_shape == 1 || block_shape == 2 || block_shape == 6 || block_shape == 7,
+             "sa_conv2d_k3_wino4_multi: block_shape 0, 1, 2, 6 or 7 (got %d)", block_shape);
   // Large blocks unless the caller asks for small ones (block_shape 2).  The small shape measured
   // 2-8% faster on standalone launches of Cin <= 128 with a few rounds of blocks (qh08, convc2) but
   // not faster in the forward as a blanket choice.  block_shape 6: the split kernel (W4Split;
-  // filters from sa_conv2d_wino4_weights_split).
-  const bool small = block_shape == 2, split = block_shape == 6;
+  // filters from sa_conv2d_wino4_weights_split).  block_shape 7: the half kernel (W4Half: the same
+  // filters, guard and preconditions as 6; the transformed input as a single f16).
+  const bool small = block_shape == 2, half = block_shape == 7, split = block_shape == 6 || half;
   const int nt = small ? W4Small::NT : W4Big::NT;
   constexpr int CO = 32;
   const int aff_max = small ? W4Small::AFF_MAX : split ? W4Split::AFF_MAX : W4Big::AFF_MAX;
@@ -1350,9 +1390,9 @@ extern "C" int sa_conv2d_k3_wino4_launch(int nprob, const SaWinoProblem *probs, 
       auto a16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
       SA_REQUIRE(e.mode >= 1 && e.mode <= 3, "sa_conv2d_k3_wino4: gate mode %d", e.mode);
       if (e.mode == 3) {
-        SA_REQUIRE(e.head_w && e.head_part && !q.stats_partial && !q.pitch && (block_shape == 0 || block_shape == 6),
+        SA_REQUIRE(e.head_w && e.head_part && !q.stats_partial && !q.pitch && (block_shape == 0 || split),
                    "sa_conv2d_k3_wino4: the flow-head epilogue needs head_w / head_part, no statistics, dense "
-                   "planes and the 8-wave 32-channel shape (block_shape 0 or 6)");
+                   "planes and the 8-wave 32-channel shape (block_shape 0, 6 or 7)");
         SA_REQUIRE(e.head_part_bs >= sa_flow_head_part_size(1, q.Cout, q.H, q.W),
                    "sa_conv2d_k3_wino4: head_part_bs too small");
         L.gate[i] = W4Gate{};
@@ -1397,7 +1437,11 @@ extern "C" int sa_conv2d_k3_wino4_launch(int nprob, const SaWinoProblem *probs, 
   L.guard = split && guard ? 1 : 0;
   hipStream_t s = sa::as_stream(stream);
   sa::TimingScope ts(SA_K_CONV2D_W4, s);
-  if (split) {
+  if (half) {
+    aff     ? wino_f4k3_kernel<W4Half, false, true><<<(unsigned)total, W4Half::NTHR, 0, s>>>(L)
+    : gated ? wino_f4k3_kernel<W4Half, true><<<(unsigned)total, W4Half::NTHR, 0, s>>>(L)
+            : wino_f4k3_kernel<W4Half, false><<<(unsigned)total, W4Half::NTHR, 0, s>>>(L);
+  } else if (split) {
     aff     ? wino_f4k3_kernel<W4Split, false, true><<<(unsigned)total, W4Split::NTHR, 0, s>>>(L)
     : gated ? wino_f4k3_kernel<W4Split, true><<<(unsigned)total, W4Split::NTHR, 0, s>>>(L)
             : wino_f4k3_kernel<W4Split, false><<<(unsigned)total, W4Split::NTHR, 0, s>>>(L);

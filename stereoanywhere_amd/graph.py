@@ -38,7 +38,8 @@ class ForwardGraph:
         from . import _native as N
         # everything that picks the captured kernels: the schedule, the module-level kernel
         # switches and the library's own A/B switches (set by A/B scripts and tests) and the
-        # model's flags
+        # model's flags, and whether this call runs in mixed precision (a default capture is never
+        # replayed for a mixed call, nor the reverse)
         args = tuple(sorted((k, repr(v)) for k, v in vars(m.args).items()))
         lib = N.lib()
         # (an A/B run's older library, SA_HIP_LIB, may lack a getter: its switch reads as None)
@@ -50,7 +51,7 @@ class ForwardGraph:
                 m.stream_overlap, m._derived_key, (ops._WINO4, ops.W4_SPLIT, ops.DIRECT_SPLIT, ops._WINO4_MIN_BLOCKS,
                                                    ops.SPLIT_GUARD, ops.CONV3D_MFMA, ops.CONV1X1,
                                                    encoders.FNET_LAZY_CLOSE, encoders.DIRECT_SMALL),
-                c_switches, args)
+                c_switches, args, m.mixed_precision_active())
 
     def __call__(self, image2, image3, mde2, mde3, iters: int = 12, test_mode: bool = True):
         if not test_mode:

@@ -23,8 +23,9 @@ The observable behaviour is the reference's:
 * ``release_cache`` (default False) empties the caching allocator after the forward as the
   reference always does (line 82); on MI355X that only forces re-allocation next call.
 
-The model computes fp32: ``mixed_precision`` reaches the wrapped model through ``kwargs``
-as in the reference (where the tiler drops it) and autocast is not entered.
+Mixed precision: a ``mixed_precision=True`` keyword argument enters ``torch.autocast`` of the
+input's device type around the mono model's and the wrapped model's calls, as the reference does
+(cpu_offload_wrapper.py:66, 78), and still reaches the wrapped model through ``kwargs``.
 """
 from __future__ import annotations
 
@@ -33,6 +34,8 @@ from typing import Iterator, Optional
 
 import torch
 import torch.nn as nn
+
+from .tiler import model_autocast
 
 Tensor = torch.Tensor
 
@@ -76,10 +79,11 @@ class CPUOffloadWrapper(nn.Module):
     def forward(self, left: Tensor, right: Tensor, mono_left: Optional[Tensor] = None,
                 mono_right: Optional[Tensor] = None, *args, **kwargs):
         device = left.device
+        mixed = bool(kwargs.get("mixed_precision", False))
         if mono_left is None or mono_right is None:
             if self.mono_model is None:
                 raise ValueError("Monocular model required when mono inputs absent")
-            with temporarily_to(self.mono_model, device):
+            with temporarily_to(self.mono_model, device), model_autocast(device.type, mixed):
                 mono_left, mono_right = self.mono_model(left, right)
             if self.offload_mono:
                 if self.host_roundtrip:
@@ -91,7 +95,8 @@ class CPUOffloadWrapper(nn.Module):
                 mono_left = mono_left.to(device)
             if mono_right is not None and mono_right.device != device:
                 mono_right = mono_right.to(device)
-            disparity = self.model(left, right, mono_left, mono_right, *args, **kwargs)
+            with model_autocast(device.type, mixed):
+                disparity = self.model(left, right, mono_left, mono_right, *args, **kwargs)
         if self.release_cache and device.type == "cuda":
             torch.cuda.empty_cache()
         return disparity

@@ -7,6 +7,7 @@ PyTorch is plumbing here (device memory, streams); the arithmetic is in the .so.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import math
@@ -1109,11 +1110,40 @@ def _gate_epilogue(p: dict) -> "N.SaGateEpilogue":
 SPLIT_GUARD = True
 
 
+# Mixed precision (ops.mixed_precision): every F(4x4) launch that would take the split kernel
+# (block_shape 6) takes its single-f16-operand form instead (block_shape 7: hi = f16(V) against the
+# exact filter pairs, fp32 sums).  Launches that are not split-eligible (u4s None, small blocks, the
+# F(2x2) kernel) keep their fp32 products.  Module state, read when a launch is enqueued.
+_MIXED = False
+# F(4x4) launches per block shape ({0, 2, 6, 7}: count); a test clears it.  (Apart from WORK,
+# whose keys bench.py reads.)
+W4_SHAPE_LAUNCHES: dict = {}
+
+
+@contextlib.contextmanager
+def mixed_precision(enabled: bool = True):
+    """Run the split-eligible F(4x4,3x3) convs enqueued inside with single-f16 Winograd-domain
+    inputs (block_shape 7).  Default off; nests; restores the previous state on exit."""
+    global _MIXED
+    prev, _MIXED = _MIXED, bool(enabled)
+    try:
+        yield
+    finally:
+        _MIXED = prev
+
+
+def mixed_precision_enabled() -> bool:
+    return _MIXED
+
+
 def _wino4_launch(n: int, arr, gates, shape: int, x: torch.Tensor) -> None:
-    """sa_conv2d_k3_wino4_launch; the split shape (6) with its range guard (an overflowed block
-    recomputes itself on fp32 products inside the launch)."""
+    """sa_conv2d_k3_wino4_launch; the split shape (6, or 7 under mixed_precision) with its range
+    guard (an overflowed block recomputes itself on scaled inputs inside the launch)."""
+    if shape == 6 and _MIXED:
+        shape = 7
+    W4_SHAPE_LAUNCHES[shape] = W4_SHAPE_LAUNCHES.get(shape, 0) + 1
     N.call("sa_conv2d_k3_wino4_launch", n, ctypes.addressof(arr), ctypes.addressof(gates), shape,
-           1 if (shape == 6 and SPLIT_GUARD) else 0, _stream(x))
+           1 if (shape in (6, 7) and SPLIT_GUARD) else 0, _stream(x))
 
 
 def conv2d_k3_multi(*problems, small_blocks: bool = False) -> list:
@@ -1162,6 +1192,8 @@ def conv2d_k3_multi(*problems, small_blocks: bool = False) -> list:
                                                   for p in problems])
         _wino4_launch(len(built), arr, gates, 2 if small_blocks else 6 if split else 0, problems[0]["x"])
     else:
+        if f4:
+            W4_SHAPE_LAUNCHES[0] = W4_SHAPE_LAUNCHES.get(0, 0) + 1
         N.call("sa_conv2d_k3_wino4_multi" if f4 else "sa_conv2d_k3_wino_multi", len(built), ctypes.addressof(arr),
                _stream(problems[0]["x"]))
     return [b[1]() for b in built]

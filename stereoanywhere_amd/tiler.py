@@ -23,12 +23,17 @@ Multi-GPU: with ``rank``/``world`` set, rank r processes unique tiles r, r+world
 stitched and weight maps are summed with one all_reduce (RCCL over xGMI) — the tiled
 path's only exchange.
 
-The model computes fp32 throughout: ``mixed_precision`` is accepted for API compatibility
-and, like the reference's tiled path (tile_wrapper.py:135 pops it from **kwargs, so the
-keyword argument never reaches autocast), does not change the arithmetic.
+Mixed precision: ``TileWrapper.forward(mixed_precision=True)`` and ``MapReduceInference(
+mixed_precision=True)`` (guidance pass and tile pass) call the wrapped model under
+``torch.autocast(<device type>)``, as the reference does (tile_wrapper.py:238, 305,
+tiled_inference.py:197, 306); ``StereoAnywhere`` answers autocast with its mixed-precision mode
+(model.py).  The reference's ``TileWrapper.forward`` overwrites its named argument with
+``kwargs.pop("mixed_precision", False)`` (tile_wrapper.py:136), which is always False there, so
+the reference's tiles always run fp32; this one does what the flag says.
 """
 from __future__ import annotations
 
+import contextlib
 import hashlib
 import math
 from dataclasses import dataclass
@@ -140,6 +145,12 @@ def blend_weight(height: int, width: int, device) -> torch.Tensor:
     return torch.clamp(w, min=1e-4)
 
 
+def model_autocast(device_type: str, enabled: bool):
+    """The context the harness calls a wrapped model in: torch.autocast(device_type) when mixed
+    precision is asked for, nothing otherwise (an enclosing autocast is left as it is)."""
+    return torch.autocast(device_type) if enabled else contextlib.nullcontext()
+
+
 def _hip_tiles(*ts) -> bool:
     """The GPU gather / stitch (ops.tile_gather_pad / tile_stitch) take float32 CUDA images of batch 1;
     anything else (CPU tensors: the harness tests' mock models) keeps the torch ops."""
@@ -209,12 +220,13 @@ class TileWrapper(torch.nn.Module):
     def _enumerate_tiles(self, height: int, width: int) -> List[TileSpec]:
         return enumerate_tiles(height, width, self.tile_height, self.tile_width, self.overlap)
 
-    def _run(self, left, right, ml, mr, args, kw):
+    def _run(self, left, right, ml, mr, args, kw, mixed: bool = False):
         _pad = pad32(*left.shape[-2:])
 
         def pad(t):
             return None if t is None else F.pad(t, _pad, mode="replicate")
-        disp = canonicalize(self.model(pad(left), pad(right), pad(ml), pad(mr), *args, **kw))
+        with model_autocast(left.device.type, mixed):
+            disp = canonicalize(self.model(pad(left), pad(right), pad(ml), pad(mr), *args, **kw))
         hd, wd = disp.shape[-2:]
         return disp[..., _pad[2]:hd - _pad[3], _pad[0]:wd - _pad[1]]
 
@@ -230,7 +242,8 @@ class TileWrapper(torch.nn.Module):
             raise ValueError("TileWrapper currently supports batch size == 1")
         if H <= self.tile_height and W <= self.tile_width:
             self.last_tile_counts = (1, 1)
-            return canonicalize(self.model(left, right, mono_left, mono_right, *args, **kw))
+            with model_autocast(left.device.type, mixed_precision):
+                return canonicalize(self.model(left, right, mono_left, mono_right, *args, **kw))
         guide = None
         if global_guidance is not None and guidance_weight > 0:
             guide = global_guidance
@@ -264,7 +277,8 @@ class TileWrapper(torch.nn.Module):
 
             def gp(t):
                 return None if t is None else ops.tile_gather_pad(t.contiguous(), org, th, tw, _pad)
-            disp = canonicalize(self.model(gp(left), gp(right), gp(mono_left), gp(mono_right), *args, **kw))
+            with model_autocast(left.device.type, mixed_precision):
+                disp = canonicalize(self.model(gp(left), gp(right), gp(mono_left), gp(mono_right), *args, **kw))
             hd, wd = disp.shape[-2:]
             outs = disp[..., _pad[2]:hd - _pad[3], _pad[0]:wd - _pad[1]]
             if guide is None and outs.device == device and outs.shape[-2:] == (th, tw):
@@ -286,10 +300,11 @@ class TileWrapper(torch.nn.Module):
             outs = self._run(torch.cat([view(left, s) for s in mine]), torch.cat([view(right, s) for s in mine]),
                              None if mono_left is None else torch.cat([view(mono_left, s) for s in mine]),
                              None if mono_right is None else torch.cat([view(mono_right, s) for s in mine]),
-                             args, kw)
+                             args, kw, mixed_precision)
             outs = list(outs.split(1, 0))
         else:
-            outs = [self._run(view(left, s), view(right, s), view(mono_left, s), view(mono_right, s), args, kw)
+            outs = [self._run(view(left, s), view(right, s), view(mono_left, s), view(mono_right, s), args, kw,
+                              mixed_precision)
                     for s in mine]
         done = {}
         for s, d in zip(mine, outs):
@@ -463,7 +478,7 @@ class MapReduceInference:
             ml, mr = (F.interpolate(m, size=(th, tw), mode="bilinear", align_corners=False) for m in mono_pair)
         elif self.mono_model is not None:
             ml, mr = self.mono_model(lt, (th, tw)), self.mono_model(rt, (th, tw))
-        with torch.no_grad():
+        with torch.no_grad(), model_autocast(torch.device(device).type, self.mixed_precision):
             low = canonicalize(self.stereo_model(lt, rt, ml, mr, iters=32, test_mode=True)).float()
         # cv2.resize(INTER_LINEAR) up-sampling == half-pixel bilinear with edge clamping
         g = F.interpolate(low.cpu(), size=(h, w), mode="bilinear", align_corners=False)[0, 0].numpy()
@@ -496,7 +511,7 @@ class MapReduceInference:
             guide = guide.to(device=device, dtype=dtype)
             if guidance_weight == 0.3:   # the default -> the instance's weight (298-299)
                 guidance_weight = self.guidance_weight
-        with torch.no_grad():
+        with torch.no_grad(), model_autocast(torch.device(device).type, self.mixed_precision):
             disp = self.tile_wrapper(inputs.left, inputs.right, inputs.mono_left, inputs.mono_right,
                                      mixed_precision=self.mixed_precision, global_guidance=guide,
                                      guidance_weight=guidance_weight, **kwargs)

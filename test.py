@@ -126,7 +126,9 @@ def run(net, sample, args, device, mono_model=None):
     if args.stereomodel == "skip_pred":   # test.py:219-220, 227-228: zero prediction, no network
         pred = torch.zeros_like(P(im2))[:, 0]
     else:
-        flow_up, _ = net(P(im2), P(im3), P(m2), P(m3), test_mode=True, iters=args.iters)
+        # test.py:215: the forward under autocast when --mixed_precision is given
+        with tiler.model_autocast(torch.device(device).type, getattr(args, "mixed_precision", False)):
+            flow_up, _ = net(P(im2), P(im3), P(m2), P(m3), test_mode=True, iters=args.iters)
         pred = -flow_up[:, 0]
     hd, wd = pred.shape[-2:]
     pred = pred[..., pad[2]:hd - pad[3], pad[0]:wd - pad[1]]
