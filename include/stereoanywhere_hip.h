@@ -29,12 +29,13 @@ extern "C" {
  * that sa_abi_version() == SA_ABI_VERSION and that sa_struct_size(SA_STRUCT_*) equals its own
  * sizeof: the arrays of SaWinoProblem / SaGateEpilogue / SaResampleJob are read at the library's
  * stride, so a host built against another layout would hand over misread fields.
+ *   9: sa_corr_lookup_backward / sa_corr_pyramid_backward / sa_corr_volume_backward (additive)
  *   8: block_shape 7 of sa_conv2d_k3_wino4_multi_gate / sa_conv2d_k3_wino4_launch (additive)
  *   7: sa_feature_gates / SaFeatureGateJob added (additive: no earlier entry point changed)
  *   6: round 6 (the implicit-GEMM entry points removed; sa_struct_size, sa_conv3d_mf_get_planes)
  *   5: SaWinoProblem gained the residual-epilogue fields (skip ... out_act); sa_conv2d_k3_wino4_launch
  *      took a guard flag; sa_conv2d_wino4_weights_cb removed */
-#define SA_ABI_VERSION 8
+#define SA_ABI_VERSION 9
 enum { SA_STRUCT_WINO_PROBLEM = 0, SA_STRUCT_GATE_EPILOGUE = 1, SA_STRUCT_RESAMPLE_JOB = 2, SA_STRUCT_FEATURE_GATE_JOB = 3 };
 int sa_abi_version(void);
 /* sizeof the struct `which` (SA_STRUCT_*) as the library was built, -1 for an unknown id */
@@ -94,6 +95,37 @@ int sa_corr_pyramid_from_volume_strided(const float *volume, int B, int H, int W
 int sa_corr_lookup(const float *pyramid_a, const float *pyramid_b, int W2, long row_stride,
                    int num_levels, int radius, const float *coords_x, long coords_bstride,
                    int B, int H, int W1, float *out, long out_bstride, void *stream);
+
+/* Backward of the correlation plug-in (corr_backward.hip): three adjoints, all fp32, all
+ * deterministic (no floating-point atomics, a fixed summation order, the same bits every run).
+ *
+ * Adjoint of sa_corr_lookup with respect to one pyramid (coordinates get no gradient: the
+ * reference detaches them every iteration, stereoanywhere.py:268).
+ *   grad_out: element (b, l*(2r+1) + t, h, j) at grad_out[b*grad_bstride + (l*(2r+1) + t)*H*W1 + h*W1 + j]
+ *   coords_x: as sa_corr_lookup
+ *   grad_pyramid [B*H*W1, row_stride]: EVERY float of every row is written; cells no tap reaches
+ *     and the padding from sa_pyramid_level_offset(W2, num_levels) to row_stride are 0.0f.
+ *   Per pixel, from zeros, for l ascending and t ascending: row_l[xi] += g e, row_l[xi+1] += g w
+ *   with xi, w, e the forward's own fp32 values for that tap (cells outside [0, W_l - 1] dropped).
+ * Same domain and refusals as sa_corr_lookup (1..4 levels, radius 0..16, coarsest level >= 2 wide). */
+int sa_corr_lookup_backward(const float *grad_out, long grad_bstride, const float *coords_x, long coords_bstride,
+                            int B, int H, int W1, int W2, int num_levels, int radius, float *grad_pyramid,
+                            long row_stride, void *stream);
+
+/* Adjoint of the avg-pool pyramid (sa_corr_pyramid_from_volume):
+ *   grad_volume[row][k] = sum over l with (k >> l) < W_l of 2^-l grad_pyramid[row][off_l + (k >> l)],
+ *   l ascending; rows of W2 floats at stride out_row_stride >= W2. */
+int sa_corr_pyramid_backward(const float *grad_pyramid, long rows, int W2, long row_stride, int num_levels,
+                             float *grad_volume, long out_row_stride, void *stream);
+
+/* Adjoint of CorrBlock1D.corr (sa_corr_volume_pyramid at one level, no truncation), fp32 MFMA:
+ *   grad_volume: element (b,h,j,k) at grad_volume[((b*H + h)*W1 + j)*vol_row_stride + k]
+ *   grad_fmap2[b,c,h,j] = (sum_k G[b,h,j,k] fmap3[b,c,h,k]) / sqrt_c   (k ascending)
+ *   grad_fmap3[b,c,h,k] = (sum_j G[b,h,j,k] fmap2[b,c,h,j]) / sqrt_c   (j ascending)
+ * Either output may be NULL to skip it (not both).  Any C, W1, W2 >= 1. */
+int sa_corr_volume_backward(const float *grad_volume, long vol_row_stride, const float *fmap2, const float *fmap3,
+                            int B, int C, int H, int W1, int W2, float sqrt_c, float *grad_fmap2,
+                            float *grad_fmap3, void *stream);
 
 /* a2 — estimate_normals (utils.py:73-77) on the 1/4-res mono map.
  *   mde [B,1,H,W] -> normals [B,3,H,W]; gain = W/normal_gain (stereoanywhere.py:113). */

@@ -68,6 +68,9 @@ SIGNATURES = {
     "sa_corr_pyramid_from_volume_strided": (I, [P, I, I, I, I, L, L, L, I, P, L, P]),
     "sa_corr_lookup": (I, [P, P, I, L, I, I, P, L, I, I, I, P, L, P]),
     "sa_corr_lookup_conv1x1": (I, [P, P, I, L, I, I, P, L, I, I, I, P, P, I, P, P]),
+    "sa_corr_lookup_backward": (I, [P, L, P, L, I, I, I, I, I, I, P, L, P]),
+    "sa_corr_pyramid_backward": (I, [P, L, I, L, I, P, L, P]),
+    "sa_corr_volume_backward": (I, [P, L, P, P, I, I, I, I, I, F, P, P, P]),
     "sa_lookup_set_mfma": (None, [I]),
     "sa_lookup_set_shear_dual": (None, [I]),
     "sa_lookup_get_shear_dual": (I, []),
@@ -207,7 +210,7 @@ def lib() -> ctypes.CDLL:
 
 # include/stereoanywhere_hip.h SA_ABI_VERSION: the library must be built from the same header as
 # these bindings (the struct arrays are read at the library's stride)
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 def _check_abi(h) -> None:

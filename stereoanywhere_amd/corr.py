@@ -10,14 +10,78 @@ selected by ``args.corr_implementation`` (stereoanywhere.py:25, 128-133).
 of a pixel row back to back (include/stereoanywhere_hip.h) and ``corr_pyramid`` exposes
 per-level views shaped like the reference's.  ``HipCorrBlock1D.from_features`` is the
 fused entry (volume + truncation + pyramid in one kernel) the model uses.
+
+The three contract methods are differentiable (csrc/corr_backward.hip): with grad mode on and an
+input that requires grad they run as the autograd functions below, otherwise they make the plain
+``ops`` calls of the inference path and return tensors without a ``grad_fn``.  Coordinates get no
+gradient; ``__call__`` raises on coordinates that require grad.
 """
 from __future__ import annotations
 
 from typing import Optional, Sequence
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import ops
+
+
+def _wants_grad(*tensors) -> bool:
+    """Grad mode is on and one of the tensors requires grad: the autograd functions below are
+    used; otherwise the contract methods make the plain ``ops`` calls of the inference path."""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+class _CorrVolumeFn(torch.autograd.Function):
+    """ops.corr_volume with ops.corr_volume_backward as its adjoint (double backward is not built)."""
+
+    @staticmethod
+    def forward(ctx, fmap2, fmap3):
+        ctx.save_for_backward(fmap2, fmap3)
+        return ops.corr_volume(fmap2, fmap3)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        fmap2, fmap3 = ctx.saved_tensors
+        need2, need3 = ctx.needs_input_grad
+        if not (need2 or need3):
+            return None, None
+        return ops.corr_volume_backward(grad.contiguous(), fmap2, fmap3, need2, need3)
+
+
+class _PyramidFn(torch.autograd.Function):
+    """ops.pyramid_from_volume of a [rows, W2] volume with ops.pyramid_backward as its adjoint."""
+
+    @staticmethod
+    def forward(ctx, volume, num_levels):
+        ctx.geo = (volume.shape[-1], num_levels)
+        return ops.pyramid_from_volume(volume, num_levels)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        W2, num_levels = ctx.geo
+        return ops.pyramid_backward(grad.contiguous(), W2, num_levels), None
+
+
+class _LookupFn(torch.autograd.Function):
+    """ops.corr_lookup of one pyramid with ops.corr_lookup_backward as its adjoint with respect to
+    the pyramid buffer.  The coordinates get no gradient (the caller has checked that they ask
+    for none): the reference detaches them at the top of every iteration (stereoanywhere.py:268)."""
+
+    @staticmethod
+    def forward(ctx, pyramid, coords_x, W2, num_levels, radius):
+        ctx.save_for_backward(coords_x)
+        ctx.geo = (W2, num_levels, radius, pyramid.shape[1])
+        return ops.corr_lookup(pyramid, None, W2, num_levels, radius, coords_x)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        coords_x, = ctx.saved_tensors
+        W2, num_levels, radius, rs = ctx.geo
+        return ops.corr_lookup_backward(grad.contiguous(), coords_x, W2, num_levels, radius, rs), None, None, None, None
 
 
 class HipCorrBlock1D:
@@ -34,7 +98,10 @@ class HipCorrBlock1D:
             if fullcorr.dim() != 5 or fullcorr.shape[3] != 1:
                 raise RuntimeError(f"fullcorr must be [B,H,W1,1,W2], got {tuple(fullcorr.shape)}")
             B, H, W1, _, W2 = fullcorr.shape
-            _pyramid = ops.pyramid_from_volume(fullcorr.reshape(B * H * W1, W2), num_levels)
+            if _wants_grad(fullcorr):   # the buffer stays in the graph: every lookup's gradient sums into it
+                _pyramid = _PyramidFn.apply(fullcorr.reshape(B * H * W1, W2), num_levels)
+            else:
+                _pyramid = ops.pyramid_from_volume(fullcorr.reshape(B * H * W1, W2), num_levels)
             _shape = (B, H, W1, W2)
         self.shape = _shape
         self.pyramid = _pyramid
@@ -53,7 +120,10 @@ class HipCorrBlock1D:
             views = [self.pyramid[:, o:o + w].unsqueeze(1).unsqueeze(1) for o, w in zip(offs, wids)]
             last = views[-1].reshape(-1, wids[-1])
             if wids[-1] >= 2:
-                extra = ops.pyramid_from_volume(last.contiguous(), 2)
+                if _wants_grad(last):
+                    extra = _PyramidFn.apply(last.contiguous(), 2)
+                else:
+                    extra = ops.pyramid_from_volume(last.contiguous(), 2)
                 w = wids[-1] // 2
                 views.append(extra[:, wids[-1]:wids[-1] + w].unsqueeze(1).unsqueeze(1))
             else:   # avg_pool2d of a width-1 (or 0) row is empty
@@ -109,12 +179,19 @@ class HipCorrBlock1D:
                                        self.num_levels, self.radius, coords_x, weight_kc, bias, out)
 
     def __call__(self, coords: torch.Tensor) -> torch.Tensor:
+        if torch.is_grad_enabled() and coords.requires_grad:
+            raise RuntimeError("HipCorrBlock1D: the lookup has no gradient with respect to the coordinates; "
+                               "detach the coordinates first (coords.detach(), as the reference does at the top "
+                               "of every iteration)")
         x = coords[:, :1]
         if self.pad[0]:
             x = x + self.pad[0]
         if not x.is_contiguous() and x.stride(3) != 1:
             x = x.contiguous()
-        out = ops.corr_lookup(self.pyramid, None, self.shape[3], self.num_levels, self.radius, x)
+        if _wants_grad(self.pyramid):
+            out = _LookupFn.apply(self.pyramid, x, self.shape[3], self.num_levels, self.radius)
+        else:
+            out = ops.corr_lookup(self.pyramid, None, self.shape[3], self.num_levels, self.radius, x)
         W1 = out.shape[-1]
         if self.pad[0] or self.pad[1]:
             out = out[..., self.pad[0]:W1 - self.pad[1]].contiguous()
@@ -122,24 +199,36 @@ class HipCorrBlock1D:
 
     @staticmethod
     def corr(fmap2: torch.Tensor, fmap3: torch.Tensor) -> torch.Tensor:
-        return ops.corr_volume(fmap2.float().contiguous(), fmap3.float().contiguous())
+        fmap2, fmap3 = fmap2.float().contiguous(), fmap3.float().contiguous()
+        if _wants_grad(fmap2, fmap3):
+            return _CorrVolumeFn.apply(fmap2, fmap3)
+        return ops.corr_volume(fmap2, fmap3)
 
 
 class CorrSampler(torch.autograd.Function):
     """Replacement of the reference's native-sampler hook (corr.py:17-29,
     ``corr_sampler.forward(volume [B,H,W1,W_i], coords [B,1,H,W1], radius)`` -> the 2r+1 taps
     of one pyramid level at x = coords, linear interpolation, zero outside [0, W_i - 1]).
-    Forward only (the inference tier): one HIP lookup over a one-level pyramid."""
+    One HIP lookup over a one-level pyramid; backward returns the volume's gradient (the lookup's
+    and the pyramid's adjoints at one level) and, as RAFT's ``corr_sampler.backward``, none for the
+    coordinates.  Double backward is not built."""
 
     @staticmethod
     def forward(ctx, volume, coords, radius):
         B, H, W1, Wi = volume.shape
         pyr = ops.pyramid_from_volume(volume.contiguous().reshape(B * H * W1, Wi), 1)
-        return ops.corr_lookup(pyr, None, Wi, 1, int(radius), coords[:, :1].contiguous())
+        x = coords[:, :1].contiguous()
+        ctx.save_for_backward(x)
+        ctx.geo = (tuple(volume.shape), int(radius), pyr.shape[1])
+        return ops.corr_lookup(pyr, None, Wi, 1, int(radius), x)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, grad_output):
-        raise NotImplementedError("CorrSampler.backward: training is outside this tier")
+        x, = ctx.saved_tensors
+        shape, radius, rs = ctx.geo
+        grad_pyr = ops.corr_lookup_backward(grad_output.contiguous(), x, shape[3], 1, radius, rs)
+        return ops.pyramid_backward(grad_pyr, shape[3], 1).view(shape), None, None
 
 
 # args.corr_implementation -> block class.  The reference's "reg" (torch) and "reg_cuda"

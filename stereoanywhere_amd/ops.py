@@ -205,6 +205,75 @@ def corr_lookup(pyr_a: torch.Tensor, pyr_b: Optional[torch.Tensor], W2: int, num
     return out
 
 
+# ----------------------------------------------------------------------- backward of the plug-in
+def corr_lookup_backward(grad_out: torch.Tensor, coords_x: torch.Tensor, W2: int, num_levels: int, radius: int,
+                         row_stride: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Adjoint of corr_lookup with respect to one pyramid: grad_out [B, L*(2r+1), H, W1] and
+    coords_x [B,1,H,W1] (any batch strides) -> grad_pyramid [B*H*W1, row_stride], every float
+    written (cells no tap reaches and the row padding are 0).  Deterministic."""
+    gbs = _plane_bs(grad_out, "grad_out", grad_out.shape[1])
+    cbs = _plane_bs(coords_x, "coords_x")
+    B, _, H, W1 = coords_x.shape
+    K = 2 * radius + 1
+    if tuple(grad_out.shape) != (B, num_levels * K, H, W1):
+        raise RuntimeError(f"grad_out must be {(B, num_levels * K, H, W1)}, got {tuple(grad_out.shape)}")
+    rs = row_stride if row_stride is not None else pyramid_geometry(W2, num_levels)[0]
+    if out is None:
+        out = torch.empty((B * H * W1, rs), device=grad_out.device, dtype=torch.float32)
+    _check(out, "out")
+    if tuple(out.shape) != (B * H * W1, rs):
+        raise RuntimeError(f"out must be {(B * H * W1, rs)}, got {tuple(out.shape)}")
+    N.call("sa_corr_lookup_backward", grad_out.data_ptr(), gbs, coords_x.data_ptr(), cbs, B, H, W1, W2, num_levels,
+           radius, out.data_ptr(), rs, _stream(grad_out))
+    return out
+
+
+def pyramid_backward(grad_pyramid: torch.Tensor, W2: int, num_levels: int,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Adjoint of pyramid_from_volume: grad_pyramid [rows, row_stride] -> grad_volume [rows, W2],
+    grad_volume[k] = sum_l 2^-l grad_level_l[k >> l] (l ascending, levels floored away skipped)."""
+    _check(grad_pyramid, "grad_pyramid")
+    if grad_pyramid.dim() != 2:
+        raise RuntimeError(f"grad_pyramid must be [rows, row_stride], got {tuple(grad_pyramid.shape)}")
+    rows, rs = grad_pyramid.shape
+    if out is None:
+        out = torch.empty((rows, W2), device=grad_pyramid.device, dtype=torch.float32)
+    _check(out, "out", contiguous=False)
+    if out.dim() != 2 or out.shape[0] != rows or out.shape[1] != W2 or out.stride(1) != 1:
+        raise RuntimeError(f"out must be [rows, W2] with contiguous rows, got {tuple(out.shape)}")
+    N.call("sa_corr_pyramid_backward", grad_pyramid.data_ptr(), rows, W2, rs, num_levels, out.data_ptr(),
+           out.stride(0) if rows > 1 else max(out.stride(0), W2), _stream(grad_pyramid))
+    return out
+
+
+def corr_volume_backward(grad_volume: torch.Tensor, fmap2: torch.Tensor, fmap3: torch.Tensor,
+                         need_fmap2: bool = True, need_fmap3: bool = True):
+    """Adjoint of corr_volume: grad_volume [B,H,W1,W2] (or [B,H,W1,1,W2]; rows contiguous along
+    W2) -> (grad_fmap2 [B,C,H,W1], grad_fmap3 [B,C,H,W2]); an output that is not needed is None
+    and is not computed.  fp32 MFMA, the forward's float32 sqrt(C)."""
+    _check(fmap2, "fmap2")
+    _check(fmap3, "fmap3")
+    _check(grad_volume, "grad_volume", contiguous=False)
+    B, C, H, W1 = fmap2.shape
+    W2 = fmap3.shape[3]
+    if tuple(fmap3.shape[:3]) != (B, C, H):
+        raise RuntimeError(f"fmap shapes disagree: {tuple(fmap2.shape)} vs {tuple(fmap3.shape)}")
+    if grad_volume.numel() != B * H * W1 * W2 or grad_volume.shape[-1] != W2:
+        raise RuntimeError(f"grad_volume must be [B,H,W1,W2] = {(B, H, W1, W2)}, got {tuple(grad_volume.shape)}")
+    if not (need_fmap2 or need_fmap3):
+        raise RuntimeError("corr_volume_backward: nothing to compute")
+    g2d = grad_volume.reshape(B * H * W1, W2)   # a view where the rows are evenly strided, else a copy
+    if g2d.stride(1) != 1 or (g2d.shape[0] > 1 and g2d.stride(0) < W2):
+        g2d = g2d.contiguous()
+    vrs = g2d.stride(0) if g2d.shape[0] > 1 else W2
+    g2 = torch.empty_like(fmap2) if need_fmap2 else None
+    g3 = torch.empty_like(fmap3) if need_fmap3 else None
+    sqrt_c = float(torch.sqrt(torch.tensor(float(C), dtype=torch.float32)))
+    N.call("sa_corr_volume_backward", g2d.data_ptr(), vrs, fmap2.data_ptr(), fmap3.data_ptr(), B, C, H, W1, W2,
+           sqrt_c, _ptr(g2), _ptr(g3), _stream(fmap2))
+    return g2, g3
+
+
 def _lookup_bytes(npix: int, nvol: int, num_levels: int, radius: int, cout: int) -> float:
     """Algorithmic bytes of one fused lookup: per pixel the coordinate, per volume the 2r + 2 cells
     of each level's window and the cout output planes."""
