@@ -595,6 +595,18 @@ int sa_conv1x1_weights(const float *weight, int Cout, int Cin, void *out, void *
 int sa_conv1x1(const float *x, long x_bs, int B, int Cin, int H, int W, const void *wsplit, int Cout,
                const float *bias, float scale, float *out, long out_bs, void *stream);
 long sa_conv1x1_redo_blocks(int reset);
+/* The mask head's 1x1 conv, the softmax over the nine neighbours and the convex up-sampling of
+ * factor 4 in one kernel (mask_upsample.hip; update.py:159-162, 191 and utils.py:97-110): what
+ * sa_conv1x1 (Cout = 144) followed by sa_convex_upsample compute, without the logits in memory.
+ *   out = convex_upflow(flow, scale * (bias + W x)): x [B][Cin][H][W] (batch stride x_bs floats, any
+ *   H and W), Cin 64, 128 or 256 (anything else is SA_E_ARG), wsplit from sa_conv1x1_weights(Cout =
+ *   144), bias [144] or NULL, flow [B][1][H][W] dense, out [B][1][4H][4W] (batch stride out_bs
+ *   floats; out 16-byte aligned, out_bs % 4 == 0).  Products and range guard as sa_conv1x1;
+ *   sa_mask_upsample_redo_blocks counts the guarded blocks (reset != 0 clears; synchronises the
+ *   device).  Added within ABI version 9 (additive). */
+int sa_mask_upsample(const float *x, long x_bs, int B, int Cin, int H, int W, const void *wsplit,
+                     const float *bias, float scale, const float *flow, float *out, long out_bs, void *stream);
+long sa_mask_upsample_redo_blocks(int reset);
 /* The tiled harness's data movement (mapreduce_v2/tile_wrapper.py:226-236, 169-185, 188-189;
  * tiler.hip):
  * sa_tile_gather_pad: src [C][H][W] (dense) -> out [ntiles][C][th + pt + pb][tw + pl + pr], tile t

@@ -6,6 +6,11 @@ Drop-in for models/stereoanywhere/stereoanywhere.py:
     reference (stereoanywhere.py:21-50);
   * ``forward(image2, image3, mde2, mde3, iters=12, test_mode=False)`` (95);
     ``test_mode=True`` returns ``(flow_up [B,1,H,W] = -disparity, None)`` (296-297);
+    ``test_mode=False`` returns the reference's six-element tuple (299): one up-sampled prediction
+    per iteration, ``[None] * iters``, and the coarse stereo / mono / scaled-mono maps and the mono
+    confidence of both views at full resolution, evaluated without gradients (it belongs under
+    ``torch.no_grad()``, with ``volume_corruption_prob=0``: the training augmentations and any
+    backward through this model are not built);
   * identical parameter names (state dicts of the reference load with strict=True).
 
 Hot path, one kernel family per row:
@@ -17,7 +22,11 @@ Hot path, one kernel family per row:
   a10    stereo + mono pyramid lookups, one launch per iteration         sa_corr_lookup
   a12    GRU gates in the conv epilogues over [h | x | r*h] buffers    sa_conv2d_k3_wino4_multi_gate
   a14    convex upsampling of the final flow                            sa_convex_upsample
-Training (test_mode=False) is outside this tier and raises NotImplementedError.
+         ... of every iteration's flow (test_mode=False), with the mask head's 1x1 conv and the
+         softmax in the same kernel                                     sa_mask_upsample
+Training itself (gradients through this model, the volume-corruption augmentations) is outside this
+tier: test_mode=False with grad mode on and anything requiring grad, or with
+volume_corruption_prob > 0, raises NotImplementedError.
 use_truncate_vol / use_aggregate_mono_vol may be off (the reference CLI's store_true
 defaults, test.py:94-98).  The non-published flags run on the same kernels with torch glue
 around them: vol_downsample > 0 (the masked volume at 1/2^vd as a dense volume, the
@@ -131,6 +140,11 @@ class ScheduleOptions:
     # and finished with the coordinate update in one small reduction (ops.flow_head_update); False:
     # conv1 written out, then conv2d_k3_narrow and flow_update
     fuse_flow_head: bool = True
+    # the full-outputs forward (test_mode=False) up-samples every iteration's flow: the mask head's
+    # 1x1 conv, the softmax and the convex up-sampling in one kernel (ops.mask_upsample; the
+    # [B,144,H/4,W/4] logits are never written); False: ops.conv1x1 + ops.convex_upsample, the
+    # launches of the test-mode forward's last iteration (which does not read this option)
+    fuse_mask_upsample: bool = True
 
 
 class StereoAnywhere(nn.Module):
@@ -283,7 +297,17 @@ class StereoAnywhere(nn.Module):
     def forward(self, image2, image3, mde2, mde3, iters: int = 12, test_mode: bool = False):
         a = self.args
         if not test_mode:
-            raise NotImplementedError("training forward (test_mode=False) is outside the inference tier")
+            # the full-outputs forward evaluates the training call's tuple; training itself is not built
+            if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or any(
+                    torch.is_tensor(t) and t.requires_grad for t in (image2, image3, mde2, mde3))):
+                raise NotImplementedError(
+                    "forward(test_mode=False) evaluates the training call's outputs only: they carry no gradient "
+                    "(no backward through this model is built); call it under torch.no_grad()")
+            if a.volume_corruption_prob > 0:
+                raise NotImplementedError(
+                    f"volume_corruption_prob={a.volume_corruption_prob}: the volume-corruption training "
+                    "augmentations (stereoanywhere.py:214-251) are not built; construct the model with "
+                    "volume_corruption_prob=0 for forward(test_mode=False)")
         if a.n_downsample != 2:
             raise NotImplementedError(f"n_downsample={a.n_downsample}: only n_downsample=2 (the 1/4 grid) is built")
         if a.vol_downsample > 0 and (a.use_aggregate_stereo_vol or not a.use_aggregate_mono_vol):
@@ -306,14 +330,14 @@ class StereoAnywhere(nn.Module):
         with torch.no_grad(), cd.flags(enabled=cd.enabled, benchmark=cd.benchmark, deterministic=True,
                                        allow_tf32=cd.allow_tf32), \
                 ops.mixed_precision(mixed), torch.autocast("cuda", enabled=False):
-            return self._forward(image2, image3, mde2, mde3, iters)
+            return self._forward(image2, image3, mde2, mde3, iters, full=not test_mode)
 
     def mixed_precision_active(self) -> bool:
         """Whether a forward called now runs in mixed precision: the attribute, or an enclosing
         torch.autocast("cuda") (how the reference's harnesses ask)."""
         return bool(self.mixed_precision) or torch.is_autocast_enabled("cuda")
 
-    def _forward(self, image2, image3, mde2, mde3, iters):
+    def _forward(self, image2, image3, mde2, mde3, iters, full=False):
         a = self.args
         dw = self._weights()
         B, C, H, W = image2.shape
@@ -352,7 +376,7 @@ class StereoAnywhere(nn.Module):
         if side is not None:
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                mono = self._mono_branch(dw, mde2, mde3, mde_lr, m2l, m3l, n2, n3, B, H4, W4)
+                mono = self._mono_branch(dw, mde2, mde3, mde_lr, m2l, m3l, n2, n3, B, H4, W4, full)
         # ---- context + feature encoders: 3x3 convs on the HIP Winograd / implicit-GEMM kernels,
         # stems and stride-2 convs on the direct kernel, epilogues fused (encoders.py)
         if self.cnet.training or self.fnet.training:  # batch-statistics BatchNorm: module path
@@ -383,8 +407,9 @@ class StereoAnywhere(nn.Module):
             for t in list(mono) + list(hid) + list(ctx):
                 t.record_stream(main)
         else:
-            mono = self._mono_branch(dw, mde2, mde3, mde_lr, m2l, m3l, n2, n3, B, H4, W4)
-        vol_d, vol_c, sm2, mirror, coords_x = mono
+            mono = self._mono_branch(dw, mde2, mde3, mde_lr, m2l, m3l, n2, n3, B, H4, W4, full)
+        # (full outputs: the coarse mono maps, made on the mono stream and joined above)
+        vol_d, vol_c, sm2, mirror, coords_x, *coarse = mono
         del mono
 
         # ---- pyramids
@@ -397,7 +422,8 @@ class StereoAnywhere(nn.Module):
         # any other level count takes the row pyramid and the copy pass below)
         direct = self.opts.sheared_producers and big and a.corr_levels == 4
         if a.use_aggregate_stereo_vol:
-            stereo_blk = self._stereo_aggregate(dw, fmap2, fmap3, mde2, mde3, m2l, m3l, trunc, B, H4, W4)
+            stereo_blk, ds2, ds3 = self._stereo_aggregate(dw, fmap2, fmap3, mde2, mde3, m2l, m3l, trunc, B, H4, W4,
+                                                          full)
         else:
             stereo_blk = HipCorrBlock1D.from_features(fmap2, fmap3, a.corr_levels, a.corr_radius, trunc[0], trunc[1],
                                                       float(a.mirror_attenuation), sheared=direct)
@@ -424,11 +450,23 @@ class StereoAnywhere(nn.Module):
             # buffer is not read again)
             mono_blk.shear(release=True)
         parts = min(self.opts.loop_parts, B) if self.stream_overlap else 1
+        # full outputs: every iteration's up-sampled prediction in one buffer, allocated before the
+        # batch parts fork (each part writes its batch slice of iteration it)
+        preds = torch.empty((iters, B, 1, H, W), device=dev, dtype=f32) if full else None
         if parts <= 1:
-            return _drive(self._iterate(dw, hid, ctx, stereo_blk, mono_blk, coords_x, iters, B, H4, W4))
-        return self._iterate_parts(parts, dw, hid, ctx, stereo_blk, mono_blk, coords_x, iters, B, H4, W4)
+            res = _drive(self._iterate(dw, hid, ctx, stereo_blk, mono_blk, coords_x, iters, B, H4, W4, preds))
+        else:
+            res = self._iterate_parts(parts, dw, hid, ctx, stereo_blk, mono_blk, coords_x, iters, B, H4, W4, preds)
+        if not full:
+            return res
+        if not a.use_aggregate_stereo_vol:
+            ds2 = ds3 = None
+        dm2, dm3, cf2, cf3, smde2, smde3 = coarse
+        # stereoanywhere.py:299
+        return (list(preds.unbind(0)), [None] * iters, [ds2, dm2, smde2], [ds3, dm3, smde3], [None, cf2, None],
+                [None, cf3, None])
 
-    def _iterate_parts(self, parts, dw, hid, ctx, stereo_blk, mono_blk, coords_x, iters, B, H4, W4):
+    def _iterate_parts(self, parts, dw, hid, ctx, stereo_blk, mono_blk, coords_x, iters, B, H4, W4, preds=None):
         """The GRU loop over batch parts (pairs are independent), each on its own stream; the
         host enqueues them in turn, half an iteration at a time, and part i > 0 starts on the
         GPU once part i - 1 has finished its first half iteration.  The main stream waits for
@@ -453,7 +491,7 @@ class StereoAnywhere(nn.Module):
             with torch.cuda.stream(st):
                 gens.append(self._iterate(dw, [h[lo:hi] for h in hid], [c[lo:hi] for c in ctx],
                                           blk(stereo_blk, lo, hi), blk(mono_blk, lo, hi), coords_x[lo:hi], iters,
-                                          hi - lo, H4, W4))
+                                          hi - lo, H4, W4, None if preds is None else preds[:, lo:hi]))
         results = [None] * parts
         first = [None] * parts   # event after each part's first half iteration
         done = [False] * parts
@@ -473,8 +511,11 @@ class StereoAnywhere(nn.Module):
                     if first[i] is None:
                         first[i] = torch.cuda.Event()
                         first[i].record(st)
-        for st, r in zip(streams, results):
+        for st in streams:
             main.wait_stream(st)
+        if preds is not None:   # (written in place, allocated on the main stream)
+            return None, None
+        for r in results:
             # each part's output was allocated on its loop stream and is read by the cat on
             # main: keep the caching allocator from handing it back to that stream early
             r[0].record_stream(main)
@@ -508,10 +549,12 @@ class StereoAnywhere(nn.Module):
             ss = self._sides = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
         return ss[i]
 
-    def _mono_branch(self, dw, mde2, mde3, mde_lr, m2l, m3l, n2, n3, B, H4, W4):
+    def _mono_branch(self, dw, mde2, mde3, mde_lr, m2l, m3l, n2, n3, B, H4, W4, full=False):
         """Mono cost volume -> hourglass -> classifiers -> soft-argmin / confidence -> scale-shift
         alignment and mirror detector (stereoanywhere.py:136-205); returns (vol_d, vol_c, scaled
-        mono left, mirror map, initial coords_x)."""
+        mono left, mirror map, initial coords_x), and with ``full`` the full-resolution coarse maps
+        of the training tuple after them: the mono disparity of both views, the mono confidence of
+        both views, the scale/shift-aligned mono depth of both views (181-184, 195-197)."""
         a = self.args
         dev, f32 = mde2.device, torch.float32
         feats_l, feats_r = self._volume_features(mde2, mde3)
@@ -564,7 +607,19 @@ class StereoAnywhere(nn.Module):
                                                            float(a.lrc_th), float(a.mirror_conf_th))
         if a.init_disparity_zero:
             coords_x = torch.arange(W4, device=dev, dtype=f32).expand(B, 1, H4, W4).contiguous()
-        return vol_d, vol_c, sm2, mirror, coords_x
+        if not full:
+            return vol_d, vol_c, sm2, mirror, coords_x
+        H, W = mde2.shape[2:]
+        f = 2 ** a.n_downsample
+        dm2, dm3, cf2, cf3 = (torch.empty((B, 1, H, W), device=dev, dtype=f32) for _ in range(4))
+        ops.resample_multi(("interp", disp_lr[:, 0:1], dm2, None, None), ("interp", disp_lr[:, 1:2], dm3, None, None),
+                           ("interp", conf_lr[:, 0:1], cf2, None, None), ("interp", conf_lr[:, 1:2], cf3, None, None))
+        dm2.mul_(f)
+        dm3.mul_(f)
+        sc, sh = scale.view(B, 1, 1, 1), shift.view(B, 1, 1, 1)
+        # (the reference's sum over the single channel is the identity)
+        smde2, smde3 = (sc * mde2 + sh) * f, (sc * mde3 + sh) * f
+        return vol_d, vol_c, sm2, mirror, coords_x, dm2, dm3, cf2, cf3, smde2, smde3
 
     def _volume_features(self, mde2, mde3):
         """The hourglasses' guidance pyramids fmde2 / fmde3 (stereoanywhere.py:111-112, 122-123):
@@ -605,11 +660,12 @@ class StereoAnywhere(nn.Module):
         masked = vol * ml.unsqueeze(4) * mr.unsqueeze(3)            # [B, N, H, W1, W2]
         return masked.permute(0, 1, 4, 2, 3).contiguous()
 
-    def _stereo_aggregate(self, dw, fmap2, fmap3, mde2, mde3, m2l, m3l, trunc, B, H4, W4):
+    def _stereo_aggregate(self, dw, fmap2, fmap3, mde2, mde3, m2l, m3l, trunc, B, H4, W4, full=False):
         """use_aggregate_stereo_vol (stereoanywhere.py:147-157, 201-205, 253-255): the masked
         stereo volume through hourglass_stereo and classifier_stereo, times the truncation
-        volume, as the GRU's stereo pyramid (the coarse stereo disparities the reference also
-        forms there are not used by the test-mode forward)."""
+        volume, as the GRU's stereo pyramid; returns (block, None, None), or with ``full`` the coarse
+        stereo disparities of both views that the reference also forms there (154-157: the soft-argmin
+        of the aggregated volume before truncation, at full resolution) in place of the Nones."""
         a = self.args
         vol = ops.corr_volume(fmap2, fmap3).view(B, 1, H4, W4, W4)
         masked = self._masked_dense(vol, m2l, m3l, 0)
@@ -626,6 +682,15 @@ class StereoAnywhere(nn.Module):
             vol_s = F.conv3d(agg, dw["cls_s"], padding=1)
             del agg
         del masked
+        ds2 = ds3 = None
+        if full:
+            # (b, h, j, k) -> native [B, ., W2, H, W1] layout, as the mono branch reads vol_d
+            d_lr, _ = ops.softargmin_conf(vol_s, None, (vol_s.stride(0), W4, 1, H4 * W4), (B, H4, W4, W4))
+            H, W = mde2.shape[2:]
+            ds2, ds3 = (torch.empty((B, 1, H, W), device=vol_s.device, dtype=torch.float32) for _ in range(2))
+            ops.resample_multi(("interp", d_lr[:, 0:1], ds2, None, None), ("interp", d_lr[:, 1:2], ds3, None, None))
+            ds2.mul_(2 ** a.n_downsample)
+            ds3.mul_(2 ** a.n_downsample)
         rows = vol_s.permute(0, 1, 3, 4, 2)       # [B, 1, H, W1, W2] view
         if trunc[0] is not None:
             # truncate_corr_volume_v2 (utils.py:216-238), conf_th=None
@@ -637,13 +702,15 @@ class StereoAnywhere(nn.Module):
             rows = T * rows
         return HipCorrBlock1D(None, a.corr_levels, a.corr_radius,
                               _pyramid=ops.pyramid_from_volume(rows.contiguous(), a.corr_levels),
-                              _shape=(B, H4, W4, W4))
+                              _shape=(B, H4, W4, W4)), ds2, ds3
 
-    def _iterate(self, dw, hid, ctx, stereo_blk, mono_blk, coords_x, iters, B, H4, W4):
+    def _iterate(self, dw, hid, ctx, stereo_blk, mono_blk, coords_x, iters, B, H4, W4, preds=None):
         """The GRU loop as a generator: it yields twice per iteration (after gru16, or after the
         motion encoder where there is no gru16, and at the end) so that batch parts on separate
         streams can be enqueued in turn (_iterate_parts);
-        its return value is (flow_up, None)."""
+        its return value is (flow_up, None).  With ``preds`` ([iters, B, 1, H, W], the full-outputs
+        forward) every iteration runs the mask head and up-samples its flow into preds[it]; the
+        return value is then (None, None)."""
         ub = self.update_block
         enc = ub.encoder
         dev = coords_x.device
@@ -842,14 +909,23 @@ class StereoAnywhere(nn.Module):
                 f1 = ops.conv2d_k3(h08, dw["U_fh1"], ub.flow_head.conv1.bias, relu=True)
                 delta = ops.conv2d_k3_narrow(f1, ub.flow_head.conv2.weight, ub.flow_head.conv2.bias)
                 ops.flow_update(coords_x, delta[:, 0:1], flow, None)
-            if it == iters - 1:
+            if preds is not None or it == iters - 1:
                 # mask head (update.py:185-191): 3x3 conv + bias + ReLU on the Winograd kernel,
-                # then the 1x1 conv; x 0.25 as the reference scales it
+                # then the 1x1 conv; x 0.25 as the reference scales it.  Test mode: the last
+                # iteration only.  Full outputs (stereoanywhere.py:290-293): every iteration, the 3x3
+                # conv as a launch of its own, into this iteration's slice of preds, with the 1x1 conv,
+                # the softmax and the up-sampling in one kernel (opts.fuse_mask_upsample) or as the
+                # test-mode launches
                 m1 = ops.conv2d_k3(h08, dw["U_mask"], ub.mask[0].bias, relu=True)
-                if dw["c1_mask"] is not None:
-                    mask = ops.conv1x1(m1, dw["c1_mask"], ub.mask[2].out_channels, ub.mask[2].bias, 0.25)
+                if preds is not None and o.fuse_mask_upsample and dw["c1_mask"] is not None:
+                    ops.mask_upsample(m1, dw["c1_mask"], ub.mask[2].bias, 0.25, flow[:, 0:1].contiguous(),
+                                      out=preds[it])
                 else:
-                    mask = F.conv2d(m1, ub.mask[2].weight, ub.mask[2].bias).mul_(0.25)
-                flow_up = ops.convex_upsample(flow[:, 0:1].contiguous(), mask, 2 ** self.args.n_downsample)
+                    if dw["c1_mask"] is not None:
+                        mask = ops.conv1x1(m1, dw["c1_mask"], ub.mask[2].out_channels, ub.mask[2].bias, 0.25)
+                    else:
+                        mask = F.conv2d(m1, ub.mask[2].weight, ub.mask[2].bias).mul_(0.25)
+                    flow_up = ops.convex_upsample(flow[:, 0:1].contiguous(), mask, 2 ** self.args.n_downsample,
+                                                  out=None if preds is None else preds[it])
             yield
-        return flow_up, None
+        return (flow_up if preds is None else None), None

@@ -667,11 +667,17 @@ def flow_update(coords_x: torch.Tensor, delta: Optional[torch.Tensor], flow_a: O
                                                 + (flow_a is not None) + (flow_b is not None)))
 
 
-def convex_upsample(flow_x: torch.Tensor, mask: torch.Tensor, factor: int = 4) -> torch.Tensor:
-    """flow_x [B,1,H,W] (contiguous), mask [B,9*f*f,H,W] -> [B,1,f*H,f*W]."""
+def convex_upsample(flow_x: torch.Tensor, mask: torch.Tensor, factor: int = 4,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """flow_x [B,1,H,W] (contiguous), mask [B,9*f*f,H,W] -> [B,1,f*H,f*W] (``out``: contiguous)."""
     _check(flow_x, "flow_x")
     B, _, H, W = flow_x.shape
-    out = torch.empty((B, 1, factor * H, factor * W), device=flow_x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((B, 1, factor * H, factor * W), device=flow_x.device, dtype=torch.float32)
+    else:
+        _check(out, "out")
+        if tuple(out.shape) != (B, 1, factor * H, factor * W):
+            raise RuntimeError("convex_upsample: out shape mismatch")
     N.call("sa_convex_upsample", flow_x.data_ptr(), mask.data_ptr(), _plane_bs(mask, "mask"), B, H, W, factor,
            out.data_ptr(), _stream(flow_x))
     return out
@@ -1349,6 +1355,35 @@ def conv1x1(x: torch.Tensor, wsplit: torch.Tensor, Cout: int, bias: Optional[tor
     N.call("sa_conv1x1", x.data_ptr(), bs, B, Cin, H, W, wsplit.data_ptr(), Cout, _ptr(bias), float(scale),
            out.data_ptr(), _plane_bs(out, "out"), _stream(x))
     _account("conv1x1", 4.0 * B * (Cin + Cout) * H * W)   # bytes: x read once, out written once
+    return out
+
+
+def mask_upsample(x: torch.Tensor, wsplit: torch.Tensor, bias: Optional[torch.Tensor], scale: float,
+                  flow_x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """convex_upsample(flow_x, conv1x1(x, wsplit, 144, bias, scale), 4) in one kernel
+    (sa_mask_upsample): x [B,Cin,H,W] with Cin 64 / 128 / 256 (a channel-sliced or batch-strided
+    view of dense planes), wsplit from conv1x1_weights of the [144, Cin] mask-head weight, flow_x
+    [B,1,H,W] contiguous -> out [B,1,4H,4W] (given: dense planes, any batch stride)."""
+    bs = _plane_bs(x, "x")
+    _check(flow_x, "flow_x")
+    B, Cin, H, W = x.shape
+    if Cin not in (64, 128, 256):
+        raise RuntimeError(f"mask_upsample: Cin must be 64, 128 or 256, got {Cin}")
+    if tuple(flow_x.shape) != (B, 1, H, W):
+        raise RuntimeError(f"mask_upsample: flow_x {tuple(flow_x.shape)} != {(B, 1, H, W)}")
+    if wsplit.device != x.device or wsplit.dtype != torch.uint8 or wsplit.numel() != 2 * 2 * 144 * Cin:
+        raise RuntimeError("mask_upsample: wsplit must be conv1x1_weights of a [144, Cin] weight on x's device")
+    if bias is not None:
+        _check(bias, "bias")
+        if bias.numel() != 144:
+            raise RuntimeError("mask_upsample: bias must have 144 elements")
+    if out is None:
+        out = torch.empty((B, 1, 4 * H, 4 * W), device=x.device, dtype=torch.float32)
+    if tuple(out.shape) != (B, 1, 4 * H, 4 * W) or out.device != x.device:
+        raise RuntimeError("mask_upsample: out shape mismatch")
+    N.call("sa_mask_upsample", x.data_ptr(), bs, B, Cin, H, W, wsplit.data_ptr(), _ptr(bias), float(scale),
+           flow_x.data_ptr(), out.data_ptr(), _plane_bs(out, "out"), _stream(x))
+    _account("misc", 4.0 * B * (Cin + 1 + 16) * H * W)   # bytes: x and flow read once, out written once
     return out
 
 
