@@ -1,9 +1,9 @@
 #!/bin/bash
-# A/B of a split F(4x4) kernel change (round 6: the paired-channel MFMA loop, SA_W4_PAIR, and its
-# job-innermost filter layout) against a comparison build of conv2d_wino4.hip (e.g.
-# scripts/build_variant.sh head HEAD conv2d_wino4.hip -fno-slp-vectorize, or WORKTREE with
-# -DSA_W4_PAIR=0): the wino parity tests on the in-tree build, then per-conv times and two
-# interleaved passes of short bench lines.  usage: scripts/ab_pair.sh [variants/<name>.so]
+# A/B of a split F(4x4) kernel change (first used in round 6 for the paired-channel MFMA loop and
+# its job-innermost filter layout) against a comparison build of conv2d_wino4.hip (e.g.
+# scripts/build_variant.sh head HEAD conv2d_wino4.hip -fno-slp-vectorize): the wino parity tests
+# on the in-tree build, then per-conv times and two interleaved passes of short bench lines.
+# usage: scripts/ab_pair.sh [variants/<name>.so]
 set -uo pipefail
 cd "$GRAFT_REPO_ROOT"
 OUT=${OUT:-ab_out/pair}   # where the logs and the summary go

@@ -10,8 +10,7 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
+using sa::f32x4, sa::f16x4;
 
 __global__ __launch_bounds__(256) void clock_probe_kernel(int iters, float *__restrict__ out) {
   const int lane = threadIdx.x & 63;

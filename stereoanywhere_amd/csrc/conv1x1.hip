@@ -30,17 +30,12 @@
 
 namespace {
 
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using sa::f32x4, sa::f16x2, sa::f16x8;
 
 constexpr int C1_CO = 64, C1_PX = 128, C1_K = 32, C1_THR = 256;
 constexpr int C1_PITCH = 132;   // floats per LDS row (128 pixels + 4: the operand reads' rows 8 apart start
                                 // 32 banks apart, so a ds_read_b32 of 16 pixels x 4 k-groups is 2-way)
 constexpr float C1_WSCALE = 4096.0f;
-#ifndef SA_C1_V2
-#define SA_C1_V2 1   // the round-6 form (conv1x1_v2_kernel) for Cin <= 256; 0: the round-5 form everywhere
-#endif
 
 __device__ unsigned g_c1_redo_blocks;
 
@@ -389,7 +384,8 @@ extern "C" int sa_conv1x1(const float *x, long x_bs, int B, int Cin, int H, int 
   const _Float16 *hi = static_cast<const _Float16 *>(wsplit);
   hipStream_t s = sa::as_stream(stream);
   sa::TimingScope ts(SA_K_CONV1X1, s);
-  if (SA_C1_V2 && (Cin == 64 || Cin == 128 || Cin == 256) && Cout <= C2_COMAX && (long)Cout * P * 4 < 0x7ffffff0L) {   // (32-bit store offsets)
+  // the round-6 form (conv1x1_v2_kernel) for Cin <= 256, the round-5 form otherwise
+  if ((Cin == 64 || Cin == 128 || Cin == 256) && Cout <= C2_COMAX && (long)Cout * P * 4 < 0x7ffffff0L) {   // (32-bit store offsets)
     const long pb2 = (P + C2_PX - 1) / C2_PX;
     SA_REQUIRE(pb2 * B < (1L << 31), "sa_conv1x1: too many blocks");
     // channel tiles per wave: passes of 3 or 4 tiles, whichever wastes fewer MFMA rows (576: 9 = 3 x 3)
@@ -397,16 +393,16 @@ extern "C" int sa_conv1x1(const float *x, long x_bs, int B, int Cin, int H, int 
     const bool mt3 = (tpw + 2) / 3 * 3 < (tpw + 3) / 4 * 4;
     const unsigned g = (unsigned)(pb2 * B);
     const _Float16 *lo = hi + (long)Cout * Cin;
-#define SA_C1_V2_LAUNCH(MT, NKS) \
+#define C1_V2_LAUNCH(MT, NKS) \
   conv1x1_v2_kernel<MT, NKS><<<g, C2_THR, 0, s>>>(x, x_bs, Cin, P, hi, lo, Cout, bias, scale, out, out_bs, pb2)
     if (Cin == 64) {
-      if (mt3) SA_C1_V2_LAUNCH(3, 2); else SA_C1_V2_LAUNCH(4, 2);
+      if (mt3) C1_V2_LAUNCH(3, 2); else C1_V2_LAUNCH(4, 2);
     } else if (Cin == 128) {
-      if (mt3) SA_C1_V2_LAUNCH(3, 4); else SA_C1_V2_LAUNCH(4, 4);
+      if (mt3) C1_V2_LAUNCH(3, 4); else C1_V2_LAUNCH(4, 4);
     } else {
-      if (mt3) SA_C1_V2_LAUNCH(3, 8); else SA_C1_V2_LAUNCH(4, 8);
+      if (mt3) C1_V2_LAUNCH(3, 8); else C1_V2_LAUNCH(4, 8);
     }
-#undef SA_C1_V2_LAUNCH
+#undef C1_V2_LAUNCH
   } else {
     conv1x1_kernel<<<(unsigned)nblk, C1_THR, 0, s>>>(x, x_bs, Cin, P, hi, hi + (long)Cout * Cin, Cout, bias, scale,
                                                      out, out_bs, co_blocks, px_blocks);
@@ -415,12 +411,5 @@ extern "C" int sa_conv1x1(const float *x, long x_bs, int B, int Cin, int H, int 
 }
 
 extern "C" long sa_conv1x1_redo_blocks(int reset) {
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  unsigned v = 0;
-  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_c1_redo_blocks), sizeof v) != hipSuccess) return -1;
-  if (reset) {
-    const unsigned z = 0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_c1_redo_blocks), &z, sizeof z) != hipSuccess) return -1;
-  }
-  return v;
+  return sa::read_redo_counter(g_c1_redo_blocks, reset);
 }

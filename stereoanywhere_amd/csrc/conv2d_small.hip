@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void conv2d_small_kernel(const float *__restri
 // F1_CIN = 1: the model's call (round 6): the stereo flow's vertical channel is identically zero
 // (sa_flow_update / the flow_x resample job write 0), so its 49 taps only add exact zeros; with
 // them skipped (13 instead of 25 K steps) the sums are the same.
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using sa::f32x4;
 constexpr int F1_K = 7, F1_L = T + F1_K - 1;
 
 template <int F1_CIN>

@@ -26,7 +26,7 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using sa::f32x4;
 
 constexpr int OTH = 8, OTW = 32;             // output tile (pixels)
 constexpr int TR = OTH / 2, TC = OTW / 2;    // Winograd tiles: 4 rows x 16 cols
@@ -57,14 +57,6 @@ struct Wino {
   static_assert(OTH * OTW * COP <= 2 * VSZ + 2 * USZ, "output staging fits V + U");
   static_assert(SMEM * 4 <= 160 * 1024, "LDS budget");
 };
-
-#ifndef SA_WINO_SCHED
-#define SA_WINO_SCHED 0
-#endif
-
-#ifndef SA_WINO_WAVES_PER_EU
-#define SA_WINO_WAVES_PER_EU 2
-#endif
 
 constexpr int MAX_CIN_AFFINE = 512;
 
@@ -287,13 +279,10 @@ __device__ __forceinline__ void wino_body(const WinoProb &P, const unsigned wid)
   fetch_x(min(2, nchunks - 1));
   __syncthreads();
   transform(0);
-#ifndef SA_WINO_DIAG
-#define SA_WINO_DIAG 0   // timing diagnostics only (wrong results): 1 no side work, 2 also no barrier
-#endif
 #pragma unroll 1
   for (int k = 0; k < nchunks; ++k) {
     const int cur = k & 1, nxt = cur ^ 1;
-    if (SA_WINO_DIAG < 2) __syncthreads();
+    __syncthreads();
     const float2 *va = reinterpret_cast<const float2 *>(smem + Cfg::V_OFF + cur * Cfg::VSZ) + a_slot;
     const float2 *vb = reinterpret_cast<const float2 *>(smem + Cfg::U_OFF + cur * Cfg::USZ);
     float2 a[2][4], b[2][4][CG];
@@ -321,7 +310,6 @@ __device__ __forceinline__ void wino_body(const WinoProb &P, const unsigned wid)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       if (q < 3) load_ops(q + 1, (q + 1) & 1);
-      if (SA_WINO_DIAG == 0) {
       if (q == 0) transform_read(nxt);
       if (q == 1) transform_write(nxt, 0);
       if (q == 2) transform_write(nxt, 2);
@@ -331,21 +319,8 @@ __device__ __forceinline__ void wino_body(const WinoProb &P, const unsigned wid)
         fetch_u(min(k + 2, nchunks - 1));
         fetch_x(min(k + 3, nchunks - 1));
       }
-      }
       mfma_group(q, q & 1);
     }
-#if SA_WINO_SCHED
-    // issue order of the iteration: the first group's operand reads, then every MFMA
-    // followed by one LDS access and one VALU op; the global loads sit in the last quarter
-    __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
-#pragma unroll
-    for (int i = 0; i < 64; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x300, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
-      if (i >= 48 && i < 58) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-    }
-#endif
   }
   __syncthreads();
 
@@ -425,7 +400,7 @@ __device__ __forceinline__ void wino_body(const WinoProb &P, const unsigned wid)
 }
 
 template <int CG, bool AFF>
-__global__ __launch_bounds__(512, SA_WINO_WAVES_PER_EU) void wino_f2k3_kernel(const WinoLaunch L) {
+__global__ __launch_bounds__(512, 2) void wino_f2k3_kernel(const WinoLaunch L) {
   // The block's problem from its raw id: blocks are dealt to the 8 XCDs round-robin and every
   // problem's range starts at a multiple of 8, so each XCD gets an equal share of each
   // problem (problems differ in work per block); the L2-locality remap applies within it.

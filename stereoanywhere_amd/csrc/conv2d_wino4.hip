@@ -34,43 +34,9 @@
 
 #pragma clang fp contract(fast)
 
-// diagnostic switch (build-time)
-#ifndef SA_W4_DIAG
-#define SA_W4_DIAG 0   // timing diagnostics only (wrong results): 1 no DMA in the loop, 2 no
-                       // transform / MFMA, 3 no DMA and no barrier in the loop, 4 as 3 and no
-                       // DMA at all, 5 no column pass, 6 no row pass, 7 no filter reads in the loop,
-                       // 8 neither row nor column pass (no input transform), 9 the loop waits for
-                       // chunk kc - 1's DMAs only (the floor of a ring that issues two chunks ahead)
-#endif
-#ifndef SA_W4_PAIR
-#define SA_W4_PAIR 1   // split kernel: a lane's two channels (jobs) in one MFMA pair (w4_pair_split, round 6)
-#endif
-#ifndef SA_W4_PAIR_AFF
-// the affine-input split kernel on the paired loop too: it spills 28 B per lane (loop-invariant values
-// around the main loop, one reload per chunk in the affine pass) and is still faster: forward
-// 58.7 -> 58.1 ms/step, two interleaved passes (profiles/ab/r06_w4_pair_ab.txt)
-#define SA_W4_PAIR_AFF 1
-#endif
-#ifndef SA_W4_PAIR_AFF_HALF
-// the half (mixed-precision) kernel with the affine input stays on the unpaired loop: paired it
-// spills the same 28 B per lane, and the new instances get no spill allowance
-#define SA_W4_PAIR_AFF_HALF 0
-#endif
-#ifndef SA_W4_GJB
-#define SA_W4_GJB 4    // gate-epilogue store iterations whose plane loads go out together (mode 2)
-#endif
-#ifndef SA_W4_GJB1
-#define SA_W4_GJB1 8   // the same for mode 1 (8 / 16 measured the same, 49.99 vs 50.01 ms/step, but
-                       // with them the range guard's second body made the gated kernel spill 2 KiB)
-#endif
-
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
-using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using sa::f32x4, sa::f32x2, sa::f16x2, sa::f16x4;
 
 constexpr int NPT = 36;                   // transform points
 
@@ -78,7 +44,7 @@ constexpr int NPT = 36;                   // transform points
 // chunks, one block per CU (158 KiB of LDS).  Small (block_shape 2): 4 waves, 32 tiles,
 // 4-channel chunks, 66 KiB, two blocks per CU, so one block's first DMA wait and epilogue
 // overlap the other's MFMAs (per block ~6-8k cycles until the first chunk lands and ~9k of
-// epilogue around 6.8k per chunk, scripts/w4_clock.py); it is not faster in the forward.
+// epilogue around 6.8k per chunk, profiles/r06_w4_clock.txt); it is not faster in the forward.
 // (Measured slower and removed, in git history: a wide 64-channel shape, a quadrant shape, a
 // persistent kernel, the split products on the small shape, and the K = 32 / duplicated-read split
 // forms)
@@ -140,6 +106,19 @@ struct W4IsHalf : std::false_type {};
 template <class C>
 struct W4IsHalf<C, std::enable_if_t<C::HALF>> : std::true_type {};
 static_assert(2 * W4Small::SMEM * 4 <= 160 * 1024, "two small blocks per CU");
+// Main-loop form.  Paired: a lane's two channels (jobs) in one MFMA pair (w4_pair_split / w4_pair_half).
+// The affine-input split kernel is paired too: it spills 28 B per lane (loop-invariant values around
+// the main loop, one reload per chunk in the affine pass) and is still faster: forward 58.7 -> 58.1
+// ms/step, two interleaved passes (profiles/ab/r06_w4_pair_ab.txt).  The half (mixed-precision)
+// kernel with the affine input stays on the unpaired loop: paired it spills the same 28 B per lane,
+// and the half instances get no spill allowance.
+template <class C, bool AFF>
+constexpr bool W4Paired = C::SPLIT && C::JPC == 2 && !(W4IsHalf<C>::value && AFF);
+// Gate-epilogue store iterations whose plane loads go out together (w4_emit), real parameters of
+// the kernel but no build options
+constexpr int W4_GJB = 4;    // mode 2
+constexpr int W4_GJB1 = 8;   // mode 1 (8 / 16 measured the same, 49.99 vs 50.01 ms/step, but with them
+                             // the range guard's second body made the gated kernel spill 2 KiB)
 
 struct W4Prob {
   const float *in;
@@ -200,17 +179,9 @@ struct W4Launch {
   int guard;   // the split kernel's range guard (an overflowed block runs again on scaled inputs)
 };
 
-// x as the f16 A operand (hi, hi, lo, lo): hi = f16(x), lo = f16(x - hi) (x - hi is exact in
-// fp32; one v_fma_mix_f32 reads hi as f16), both round-to-nearest-even
-__device__ __forceinline__ f16x4 w4_split(const float x) {
-  const f16x2 hh = __builtin_convertvector(f32x2{x, x}, f16x2);
-  float l;
-  asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l) : "v"(__builtin_bit_cast(unsigned, hh)), "v"(x));
-  const f16x2 ll = __builtin_convertvector(f32x2{l, l}, f16x2);
-  return __builtin_shufflevector(hh, ll, 0, 1, 2, 3);
-}
-
-// The two channels of a lane's jobs (c and c + 4) as the A operands of one MFMA pair (SA_W4_PAIR):
+// The two channels of a lane's jobs (c and c + 4) as the A operands of one MFMA pair: hi = f16(x),
+// lo = f16(x - hi) (x - hi is exact in fp32; one v_fma_mix_f32 reads hi as f16), both
+// round-to-nearest-even;
 // ahi = (hi0, hi0, hi1, hi1), alo = (lo0, 0, lo1, 0) against B = (bhi0, blo0, bhi1, blo1), the two
 // channels' filter (hi, lo) dwords of one output channel, adjacent in the job-innermost LDS image
 // (one ds_read_b128 per point holds both groups' pairs): ahi . B = hi0 bhi0 + hi0 blo0 + hi1 bhi1 +
@@ -481,8 +452,8 @@ __device__ __forceinline__ void w4_emit(const W4Prob &P, const W4Gate *gate, con
       }
     }
   };
-  if (GT.mode == 1) gate_stores(std::integral_constant<int, SA_W4_GJB1>{}, std::integral_constant<int, 1>{});
-  else gate_stores(std::integral_constant<int, SA_W4_GJB>{}, std::integral_constant<int, 2>{});
+  if (GT.mode == 1) gate_stores(std::integral_constant<int, W4_GJB1>{}, std::integral_constant<int, 1>{});
+  else gate_stores(std::integral_constant<int, W4_GJB>{}, std::integral_constant<int, 2>{});
   }
 }
 
@@ -555,12 +526,59 @@ __device__ __forceinline__ void w4_flowhead(const W4Prob &P, const W4Gate &GT, f
   }
 }
 
-#ifdef SA_W4_CLOCK
-// diagnostic build only: per block (s_memtime, s_memrealtime) at the start and the end of wave 0,
-// then s_memtime after the first chunk's barrier and after the main loop
-__device__ unsigned long long g_w4_clock[65536][12];   // + [8] chunk 0 issued, [9] last wave's start,
-                                                      // [10] work item decoded, [11] chunk 0's filter DMA issued
-#endif
+// Block geometry as compile-time constants (the patch offsets divide by PS and PG): 2^LTW tiles per
+// block row; BH x BW output pixels; the staged patch is PR rows of PG 4-float groups per channel
+template <class C, int LTW>
+struct W4Geo {
+  static constexpr int tw = 1 << LTW, tr = C::NT >> LTW;
+  static constexpr int BH = 4 * tr, BW = 4 * tw, PG = tw + 2, PR = BH + 2, PS = PR * PG;
+};
+
+// The range guard's second pass: the scale from the block's largest input.  Scans the block's input
+// patch (every chunk, from global memory; after the producer's transform) and returns the power of
+// two that brings 100 max|d| >= max|V| below 2^15.  Two barriers; uses the start of smem.
+template <class C, bool AFF>
+__device__ __forceinline__ float w4_guard_scale(const W4Prob &P, float *smem, const int n, const int nchunks,
+                                                const int hw, const int (&po)[C::PDMA], const unsigned pcs,
+                                                const int wv, const int lane) {
+  constexpr int NWAVE = C::NW, KC = C::KC, PDMA = C::PDMA;
+  float *red = smem;   // (patch buffer 0: only chunk 0's filters are in flight, into the filter area)
+  const char *ib = reinterpret_cast<const char *>(P.in + (long)n * P.in_bs);
+  float mx = 0.0f;
+  // (8 chunks per iteration: their loads in flight together; one at a time the scan cost
+  // a round trip per chunk, ~30% of the fp32 pass it precedes)
+#pragma unroll 8
+  for (int kc = 0; kc < nchunks; ++kc)
+#pragma unroll
+    for (int j = 0; j < PDMA; ++j) {
+      const int pcj = (int)((pcs >> (4 * j)) & 15u) - 1;
+      if (pcj < 0) continue;
+      const f32x4 v = *reinterpret_cast<const f32x4 *>(ib + po[j] + (long)kc * KC * hw * 4);
+      float a = 1.0f, b = 0.0f, fl = -INFINITY;
+      if constexpr (AFF) {
+        const int pi = n * P.in_pstride + kc * KC + pcj;
+        const float m0 = P.in_m ? P.in_m[pi] : 0.0f, t0 = P.in_t ? P.in_t[pi] : 0.0f;
+        a = P.in_s ? P.in_s[pi] : 1.0f;
+        b = t0 - m0 * a;
+        fl = P.in_act ? 0.0f : -INFINITY;
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float t = __builtin_fabsf(fmaxf(v[e] * a + b, fl));
+        mx = fmaxf(mx, t < INFINITY ? t : 0.0f);
+      }
+    }
+  mx = sa::wave_max_dpp(mx);
+  if (lane == 0) red[wv] = mx;
+  __syncthreads();
+  mx = red[0];
+#pragma unroll
+  for (int w = 1; w < NWAVE; ++w) mx = fmaxf(mx, red[w]);
+  __syncthreads();   // (before chunk 0's patch DMA lands there)
+  int e2;
+  (void)frexpf(100.0f * mx, &e2);   // 100 max|d| < 2^e2
+  return mx > 0.0f ? ldexpf(1.0f, 15 - e2) : 1.0f;
+}
 
 // One work item: the block's 64 tiles x 32 output channels (HF: this wave's point-column half).
 // Returns true (block-uniform) when the split kernel's range guard found an overflow: nothing was
@@ -573,7 +591,7 @@ __device__ unsigned long long g_w4_clock[65536][12];   // + [8] chunk 0 issued, 
 template <class C, int HF, int LTW, bool GATED, bool AFF>
 __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, const unsigned wid, float *smem,
                                         float2 *atab, const bool guard = false, float xscale = 1.0f) {
-  constexpr int NWAVE = C::NW, NTHR = C::NTHR, KC = C::KC, JPC = C::JPC, NT = C::NT, PDMA = C::PDMA,
+  constexpr int NWAVE = C::NW, NTHR = C::NTHR, KC = C::KC, JPC = C::JPC, PDMA = C::PDMA,
                 UDMA = C::UDMA, UPW = C::UPW, UBUF = C::UBUF, BUF = C::BUF, PBUF = C::PBUF, OPP = C::OPP,
                 CO = C::CO, CG = C::CG, SB = C::SB, NR = C::NR;
   constexpr bool SPLIT = C::SPLIT, HALF = W4IsHalf<C>::value;
@@ -581,9 +599,8 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
   // a lane's filter operands of a point: one float, or (split) one f16 (hi, lo) pair, per group
   using f32xg = float __attribute__((ext_vector_type(CG)));
   const int Cin = P.Cin, H = P.H;
-  // block geometry as compile-time constants (the patch offsets divide by PS and PG)
-  constexpr int ltw = LTW, tw = 1 << ltw, tr = NT >> ltw;
-  constexpr int BH = 4 * tr, BW = 4 * tw, PG = tw + 2, PR = BH + 2, PS = PR * PG;
+  using Geo = W4Geo<C, LTW>;
+  constexpr int ltw = LTW, tw = Geo::tw, BH = Geo::BH, BW = Geo::BW, PG = Geo::PG, PS = Geo::PS;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -609,21 +626,13 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
     return JPC == 2 ? chunk * UBUF * 4 : (chunk >> 1) * 2 * UBUF * 4 + (chunk & 1) * SB * 4;
   };
 
+  // chunk 0's filters first: their offsets need no patch geometry
+#pragma unroll
+  for (int j = 0; j < UPW; ++j)
+    if (wv + NWAVE * j < UDMA)
+      dma16(uin, smem + PBUF + (wv + NWAVE * j) * 256, u_src(wv + NWAVE * j), u_chunk(0));
   // patch DMA: the chunk's image is [channel][PR rows][PG groups of 4 floats], dense, starting
   // at (y0 - 1, x0 - 4); wave-instruction gi fills groups 64 gi .. 64 gi + 63 (lane-linear)
-  // chunk 0's filters first: their offsets need no patch geometry
-#ifdef SA_W4_CLOCK
-  if (HF == 0 && tid == 0) g_w4_clock[blockIdx.x & 65535][10] = __builtin_amdgcn_s_memtime();
-#endif
-  if (SA_W4_DIAG != 4) {
-#pragma unroll
-    for (int j = 0; j < UPW; ++j)
-      if (wv + NWAVE * j < UDMA)
-        dma16(uin, smem + PBUF + (wv + NWAVE * j) * 256, u_src(wv + NWAVE * j), u_chunk(0));
-  }
-#ifdef SA_W4_CLOCK
-  if (HF == 0 && tid == 0) g_w4_clock[blockIdx.x & 65535][11] = __builtin_amdgcn_s_memtime();
-#endif
   const int npi = (KC * PS + 63) >> 6;
   int po[PDMA];
   // input transform: per piece j, 4 bits at 4j = the group's channel in the chunk + 1 (0: padding
@@ -640,45 +649,8 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
     po[j] = ok ? (ci * hw + y * pitch + x) * 4 : 0x7ffffff0;   // out of range: the load returns 0
     pcs |= (ok && wv + NWAVE * j < (KC * PS + 63) / 64 ? (unsigned)ci + 1u : 0u) << (4 * j);
   }
-  if constexpr (C::SPLIT) {
-    if (xscale == 0.0f) {   // the range guard's second pass: the scale from the block's largest input
-      float *red = smem;   // (patch buffer 0: only chunk 0's filters are in flight, into the filter area)
-      const char *ib = reinterpret_cast<const char *>(P.in + (long)n * P.in_bs);
-      float mx = 0.0f;
-      // (8 chunks per iteration: their loads in flight together; one at a time the scan cost
-      // a round trip per chunk, ~30% of the fp32 pass it precedes)
-#pragma unroll 8
-      for (int kc = 0; kc < nchunks; ++kc)
-#pragma unroll
-        for (int j = 0; j < PDMA; ++j) {
-          const int pcj = (int)((pcs >> (4 * j)) & 15u) - 1;
-          if (pcj < 0) continue;
-          const f32x4 v = *reinterpret_cast<const f32x4 *>(ib + po[j] + (long)kc * KC * hw * 4);
-          float a = 1.0f, b = 0.0f, fl = -INFINITY;
-          if constexpr (AFF) {
-            const int pi = n * P.in_pstride + kc * KC + pcj;
-            const float m0 = P.in_m ? P.in_m[pi] : 0.0f, t0 = P.in_t ? P.in_t[pi] : 0.0f;
-            a = P.in_s ? P.in_s[pi] : 1.0f;
-            b = t0 - m0 * a;
-            fl = P.in_act ? 0.0f : -INFINITY;
-          }
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float t = __builtin_fabsf(fmaxf(v[e] * a + b, fl));
-            mx = fmaxf(mx, t < INFINITY ? t : 0.0f);
-          }
-        }
-      mx = sa::wave_max_dpp(mx);
-      if (lane == 0) red[wv] = mx;
-      __syncthreads();
-      mx = red[0];
-#pragma unroll
-      for (int w = 1; w < NWAVE; ++w) mx = fmaxf(mx, red[w]);
-      __syncthreads();   // (before chunk 0's patch DMA lands there)
-      int e2;
-      (void)frexpf(100.0f * mx, &e2);   // 100 max|d| < 2^e2
-      xscale = mx > 0.0f ? ldexpf(1.0f, 15 - e2) : 1.0f;
-    }
+  if constexpr (SPLIT) {
+    if (xscale == 0.0f) xscale = w4_guard_scale<C, AFF>(P, smem, n, nchunks, hw, po, pcs, wv, lane);
   }
   const bool scaled = xscale != 1.0f;
   // the chunk's DMAs in three parts (part -1: all at once), spread over the first job's three
@@ -697,7 +669,6 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
       if ((part < 0 || j / C::PPART == part) && wv + NWAVE * j < UDMA)
         dma16(uin, ub + (wv + NWAVE * j) * 256, u_src(wv + NWAVE * j), us);
   };
-  auto issue = [&](int chunk, int buf) __attribute__((always_inline)) { issue_part(chunk, buf, -1); };
   auto issue_p0 = [&]() __attribute__((always_inline)) {   // chunk 0's patch (its filters went first)
 #pragma unroll
     for (int j = 0; j < PDMA; ++j)
@@ -735,8 +706,8 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
   // static priority for waves 4-7 (split kernel forward: 66.8 -> 66.5 ms/step, two interleaved passes)
   if (HF == 1) __builtin_amdgcn_s_setprio(1);
   // (issuing each piece as soon as its offset is known, ~1.6k cycles earlier, did not land chunk 0
-  // any sooner: 6.6k vs 6.2k cycles at xc08, forward 59.6 vs 59.8 ms/step, scripts/w4_clock.py)
-  if (SA_W4_DIAG != 4) issue_p0();
+  // any sooner: 6.6k vs 6.2k cycles at xc08, forward 59.6 vs 59.8 ms/step, profiles/r06_w4_clock.txt)
+  issue_p0();
   // Input transform: v -> act(v * scale + shift), scale = s, shift = t - m * s per channel
   // (in_pstride 0) or per (image, channel) (in_pstride = Cin).  Each lane transforms the
   // 4-float groups its own DMAs brought in (in the LDS, after its own vmcnt wait, before the
@@ -752,9 +723,6 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
     }
     __syncthreads();
   }
-#ifdef SA_W4_CLOCK
-  if (HF == 0 && tid == 0) g_w4_clock[blockIdx.x & 65535][8] = __builtin_amdgcn_s_memtime();
-#endif
 #pragma unroll 1
   for (int kc = 0; kc < nchunks; ++kc) {
     const int cur = kc & 1;
@@ -788,23 +756,7 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
         }
       }
     }
-    if (SA_W4_DIAG == 9 && !AFF && !scaled) {
-      // timing only: wait for chunk kc - 1's DMAs, not chunk kc's (every wave issues >= 9 pieces
-      // per chunk), i.e. the floor of a ring that issues each chunk two chunks ahead
-      if (kc == 0)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-    } else if (SA_W4_DIAG < 3 || AFF || scaled) {
-      __syncthreads();   // chunk kc landed (vmcnt(0) precedes the barrier); buffer cur ^ 1 is free
-    }
-#ifdef SA_W4_CLOCK
-    if (kc == 0 && HF == 0 && tid == 0) g_w4_clock[blockIdx.x & 65535][4] = __builtin_amdgcn_s_memtime();
-#endif
-    if (SA_W4_DIAG == 2 && kc + 1 < nchunks) issue(kc + 1, cur ^ 1);
-    if (SA_W4_DIAG == 2) continue;
+    __syncthreads();   // chunk kc landed (vmcnt(0) precedes the barrier); buffer cur ^ 1 is free
     const float *pb = smem + cur * BUF + pread;
     const float *ub = smem + cur * BUF + PBUF + uread;
     // Per job s (channel k, then k + 4) the lane reads its tile's 6 patch rows (8 floats each;
@@ -837,7 +789,7 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
         }
       }
     };
-    if constexpr (SPLIT && SA_W4_PAIR != 0 && JPC == 2 && (!AFF || (HALF ? SA_W4_PAIR_AFF_HALF : SA_W4_PAIR_AFF))) {
+    if constexpr (W4Paired<C, AFF>) {
       // both jobs' row passes first, then per column both jobs' column passes feed one MFMA pair per
       // (row, output-channel group) (w4_pair_split); a column's filter operands are read under its
       // two column passes
@@ -855,7 +807,7 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
       };
 #pragma unroll
       for (int jj = 0; jj < 3; ++jj) {
-        if ((SA_W4_DIAG == 0 || SA_W4_DIAG == 9) && kc + 1 < nchunks) {
+        if (kc + 1 < nchunks) {
           issue_part(kc + 1, cur ^ 1, jj);
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -887,71 +839,58 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
         }
         __builtin_amdgcn_sched_barrier(0);   // bound the scheduler's hoisting (register pressure)
       }
-      continue;
-    }
-    load_rows(0, 0, 6);
-    load_b(0, 0, bc);
+    } else {
+      load_rows(0, 0, 6);
+      load_b(0, 0, bc);
 #pragma unroll
-    for (int s = 0; s < JPC; ++s) {
-      if (s == 1) load_rows(1, 3, 6);
-      float t[6][3];
+      for (int s = 0; s < JPC; ++s) {
+        if (s == 1) load_rows(1, 3, 6);
+        float t[6][3];
 #pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        if (SA_W4_DIAG == 6 || SA_W4_DIAG == 8) {   // timing only: no row pass
-          t[r][0] = ra[r].y; t[r][1] = rb[r].x; t[r][2] = rc[r].x;
-        } else {
-          bt6h<HF>(ra[r].y, rb[r].x, rb[r].y, rb[r].z, rb[r].w, rc[r].x, t[r]);
-        }
-      }
-      if (s + 1 < JPC) load_rows(1, 0, 3);
+        for (int r = 0; r < 6; ++r) bt6h<HF>(ra[r].y, rb[r].x, rb[r].y, rb[r].z, rb[r].w, rc[r].x, t[r]);
+        if (s + 1 < JPC) load_rows(1, 0, 3);
 #pragma unroll
-      for (int jj = 0; jj < 3; ++jj) {
-        // the next chunk's DMA part jj goes out before column jj's pass of the first job (the
-        // chunk time is bound by the DMA's latency: one column earlier than after its MFMAs,
-        // wino4 51.0 -> 50.1 ms/step; all parts at once delay the row reads)
-        if ((SA_W4_DIAG == 0 || SA_W4_DIAG == 9) && s == 0 && kc + 1 < nchunks) {
-          issue_part(kc + 1, cur ^ 1, jj);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if (SA_W4_DIAG != 7 && (s + 1 < JPC || jj < 2)) load_b(jj < 2 ? s : s + 1, jj < 2 ? jj + 1 : 0, bn);
-        float v[6];
-        if (SA_W4_DIAG == 5 || SA_W4_DIAG == 8) {   // timing only: no column pass
-#pragma unroll
-          for (int i = 0; i < NR; ++i) v[i] = t[i][jj];
-        } else {
-          bt6(t[0][jj], t[1][jj], t[2][jj], t[3][jj], t[4][jj], t[5][jj], v);
-        }
-        if constexpr (SPLIT) {
-#pragma unroll
-          for (int i = 0; i < NR; ++i) {
-            // (half: (hi, hi, 0, 0) against the duplicated (bhi, blo) dword)
-            const f16x4 a = HALF ? __builtin_shufflevector(__builtin_convertvector(f32x2{v[i], v[i]}, f16x2),
-                                                           f16x2{(_Float16)0.0f, (_Float16)0.0f}, 0, 1, 2, 3)
-                                 : w4_split(v[i]);
-            const f16x4 b0 = __builtin_bit_cast(f16x4, f32x2{bc[i][0], bc[i][0]});
-            const f16x4 b1 = __builtin_bit_cast(f16x4, f32x2{bc[i][1], bc[i][1]});
-            acc[i][jj][0] = __builtin_amdgcn_mfma_f32_16x16x16f16(a, b0, acc[i][jj][0], 0, 0, 0);
-            acc[i][jj][1] = __builtin_amdgcn_mfma_f32_16x16x16f16(a, b1, acc[i][jj][1], 0, 0, 0);
+        for (int jj = 0; jj < 3; ++jj) {
+          // the next chunk's DMA part jj goes out before column jj's pass of the first job (the
+          // chunk time is bound by the DMA's latency: one column earlier than after its MFMAs,
+          // wino4 51.0 -> 50.1 ms/step; all parts at once delay the row reads)
+          if (s == 0 && kc + 1 < nchunks) {
+            issue_part(kc + 1, cur ^ 1, jj);
+            __builtin_amdgcn_sched_barrier(0);
           }
-        } else {
+          if (s + 1 < JPC || jj < 2) load_b(jj < 2 ? s : s + 1, jj < 2 ? jj + 1 : 0, bn);
+          float v[6];
+          bt6(t[0][jj], t[1][jj], t[2][jj], t[3][jj], t[4][jj], t[5][jj], v);
+          if constexpr (SPLIT) {
+            // every other split instance is on the paired loop: only the half kernel's one f16 here
+            static_assert(HALF, "an unpaired split config is the half config");
 #pragma unroll
-          for (int i = 0; i < NR; ++i)
+            for (int i = 0; i < NR; ++i) {
+              // (hi, hi, 0, 0) against the duplicated (bhi, blo) dword
+              const f16x4 a = __builtin_shufflevector(__builtin_convertvector(f32x2{v[i], v[i]}, f16x2),
+                                                      f16x2{(_Float16)0.0f, (_Float16)0.0f}, 0, 1, 2, 3);
+              const f16x4 b0 = __builtin_bit_cast(f16x4, f32x2{bc[i][0], bc[i][0]});
+              const f16x4 b1 = __builtin_bit_cast(f16x4, f32x2{bc[i][1], bc[i][1]});
+              acc[i][jj][0] = __builtin_amdgcn_mfma_f32_16x16x16f16(a, b0, acc[i][jj][0], 0, 0, 0);
+              acc[i][jj][1] = __builtin_amdgcn_mfma_f32_16x16x16f16(a, b1, acc[i][jj][1], 0, 0, 0);
+            }
+          } else {
 #pragma unroll
-            for (int g = 0; g < CG; ++g)
-              acc[i][jj][g] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[i], bc[i][g],
-                                                                    acc[i][jj][g], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);   // bound the scheduler's hoisting (register pressure)
+            for (int i = 0; i < NR; ++i)
+#pragma unroll
+              for (int g = 0; g < CG; ++g)
+                acc[i][jj][g] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[i], bc[i][g],
+                                                                      acc[i][jj][g], 0, 0, 0);
+          }
+          __builtin_amdgcn_sched_barrier(0);   // bound the scheduler's hoisting (register pressure)
 
 #pragma unroll
-        for (int i = 0; i < NR; ++i) bc[i] = bn[i];
+          for (int i = 0; i < NR; ++i) bc[i] = bn[i];
+        }
       }
     }
   }
   __syncthreads();
-#ifdef SA_W4_CLOCK
-  if (HF == 0 && tid == 0) g_w4_clock[blockIdx.x & 65535][5] = __builtin_amdgcn_s_memtime();
-#endif
   if constexpr (SPLIT) {   // the filters' 2^W4S_LOG2 and the inputs' xscale (exact)
     const float inv_scale = 1.0f / ((float)(1 << W4S_LOG2) * xscale);
 #pragma unroll
@@ -999,16 +938,7 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
       }
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
-        // A^T rows restricted to columns 0-2: [1,1,1] [0,1,-1] [0,1,1] [0,1,-1];
-        // columns 3-5: [1,1,0] [2,-2,0] [4,4,0] [8,-8,1]
-        f32x4 y;
-        if (HF == 0) {
-          const float p = u[a][1] + u[a][2], q = u[a][1] - u[a][2];
-          y = f32x4{u[a][0] + p, q, p, q};
-        } else {
-          const float p = u[a][0] + u[a][1], q = u[a][0] - u[a][1];
-          y = f32x4{p, 2.0f * q, 4.0f * p, 8.0f * q + u[a][2]};
-        }
+        const f32x4 y = at6h<HF>(u[a][0], u[a][1], u[a][2]);
         f32x4 *o = reinterpret_cast<f32x4 *>(ot + col * OPP + (orow + a) * BW + ocol);
         if (phase == 0) {
           *o = y;
@@ -1024,9 +954,6 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
   }
     if (phase == 0) __syncthreads();
   }
-#ifdef SA_W4_CLOCK
-  if (HF == 0 && tid == 0) g_w4_clock[blockIdx.x & 65535][6] = __builtin_amdgcn_s_memtime();
-#endif
   if constexpr (SPLIT) {
     // Range guard: an f16 operand overflow (|V| >= 65520: hi = inf, lo = -inf) makes every product
     // of that value NaN, and so the staged outputs it feeds (checked before the ReLU).  Such a
@@ -1058,9 +985,6 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
   return false;
 }
 
-#ifndef SA_W4_REDO
-#define SA_W4_REDO 1
-#endif
 template <class C, bool GATED, bool AFF = false>
 __global__ __launch_bounds__(C::NTHR, C::NW == 8 ? 1 : 2) void wino_f4k3_kernel(const W4Launch L) {
   // problem of the block from its raw id (ranges padded to multiples of 8: every XCD gets an
@@ -1076,10 +1000,6 @@ __global__ __launch_bounds__(C::NTHR, C::NW == 8 ? 1 : 2) void wino_f4k3_kernel(
   if (g - base >= nb) return;
   __shared__ __attribute__((aligned(16))) float smem[C::SMEM];
   __shared__ float2 atab[AFF ? C::AFF_MAX : 1];
-#ifdef SA_W4_CLOCK
-  unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-  if (threadIdx.x == C::NTHR - 64 && blockIdx.x < 65536) g_w4_clock[blockIdx.x][9] = t0;
-#endif
   // the first half of the waves takes point columns 0-2, the second half 3-5 (wave-uniform)
   const unsigned wid = sa::xcd_remap(g - base, nb);
   const bool guard = C::SPLIT && L.guard;
@@ -1087,10 +1007,10 @@ __global__ __launch_bounds__(C::NTHR, C::NW == 8 ? 1 : 2) void wino_f4k3_kernel(
   const W4Prob &P = L.p[pi];
   const W4Gate *gp = GATED ? &L.gate[pi] : nullptr;
   bool over;
-#define SA_W4_B(CC_, HF_, LTW_, G_, XS_) w4_body<CC_, HF_, LTW_, GATED, AFF>(P, gp, wid, smem, atab, G_, XS_)
-  if (threadIdx.x < C::NTHR / 2) over = P.ltw == 4 ? SA_W4_B(C, 0, 4, guard, 1.0f) : SA_W4_B(C, 0, 5, guard, 1.0f);
-  else over = P.ltw == 4 ? SA_W4_B(C, 1, 4, guard, 1.0f) : SA_W4_B(C, 1, 5, guard, 1.0f);
-  if constexpr (C::SPLIT && SA_W4_REDO) {
+#define W4_BODY(CC_, HF_, LTW_, G_, XS_) w4_body<CC_, HF_, LTW_, GATED, AFF>(P, gp, wid, smem, atab, G_, XS_)
+  if (threadIdx.x < C::NTHR / 2) over = P.ltw == 4 ? W4_BODY(C, 0, 4, guard, 1.0f) : W4_BODY(C, 0, 5, guard, 1.0f);
+  else over = P.ltw == 4 ? W4_BODY(C, 1, 4, guard, 1.0f) : W4_BODY(C, 1, 5, guard, 1.0f);
+  if constexpr (C::SPLIT) {
     if (over) {
       __syncthreads();   // the first pass's LDS reads are over
       if (threadIdx.x == 0) atomicAdd(&g_w4_redo_blocks, 1u);
@@ -1101,26 +1021,18 @@ __global__ __launch_bounds__(C::NTHR, C::NW == 8 ? 1 : 2) void wino_f4k3_kernel(
       asm volatile("" : "+s"(pil), "+s"(widl));
       const W4Prob &P2 = L.p[pil];
       const W4Gate *gp2 = GATED ? &L.gate[pil] : nullptr;
-#define SA_W4_B2(HF_, LTW_) w4_body<C, HF_, LTW_, GATED, AFF>(P2, gp2, widl, smem, atab, false, 0.0f)
+#define W4_BODY2(HF_, LTW_) w4_body<C, HF_, LTW_, GATED, AFF>(P2, gp2, widl, smem, atab, false, 0.0f)
       if (threadIdx.x < C::NTHR / 2) {
-        if (P2.ltw == 4) SA_W4_B2(0, 4);
-        else SA_W4_B2(0, 5);
+        if (P2.ltw == 4) W4_BODY2(0, 4);
+        else W4_BODY2(0, 5);
       } else {
-        if (P2.ltw == 4) SA_W4_B2(1, 4);
-        else SA_W4_B2(1, 5);
+        if (P2.ltw == 4) W4_BODY2(1, 4);
+        else W4_BODY2(1, 5);
       }
-#undef SA_W4_B2
+#undef W4_BODY2
     }
   }
-#undef SA_W4_B
-#ifdef SA_W4_CLOCK
-  if (threadIdx.x == 0 && g < 65536) {
-    g_w4_clock[g][0] = t0;
-    g_w4_clock[g][1] = r0;
-    g_w4_clock[g][2] = __builtin_amdgcn_s_memtime();
-    g_w4_clock[g][3] = __builtin_amdgcn_s_memrealtime();
-  }
-#endif
+#undef W4_BODY
 }
 
 // U = G g G^T for g = w[co][ci] (3x3), fp64, rounded once.  Layout
@@ -1275,12 +1187,6 @@ extern "C" int sa_conv2d_wino4_weights_split(const float *weight, int Cout, int 
   return sa::check_launch("sa_conv2d_wino4_weights_split");
 }
 
-#ifdef SA_W4_CLOCK
-extern "C" int sa_w4_clock_read(unsigned long long *out, int n) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_w4_clock), sizeof(unsigned long long) * 12 * n) == hipSuccess ? 0 : -1;
-}
-#endif
-
 extern "C" long sa_flow_head_part_size(int N, int Cout, int H, int W) {
   if (N <= 0 || Cout <= 0 || Cout % 32 || H <= 0 || W <= 0) return -1;
   const int ltw = w4_ltw(H, W), bw = 4 << ltw, bh = 4 * (W4Big::NT >> ltw);
@@ -1310,15 +1216,10 @@ long sa_direct_redo_blocks_internal(int reset);   // conv_direct.hip
 // blocks of the split kernels (F(4x4) and direct) that the range guards recomputed
 // since the last reset; synchronises the device (tests and bench.py, outside timed regions)
 extern "C" long sa_split_redo_blocks(int reset) {
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  unsigned v = 0;
-  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_w4_redo_blocks), sizeof v) != hipSuccess) return -1;
-  if (reset) {
-    const unsigned z = 0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_w4_redo_blocks), &z, sizeof z) != hipSuccess) return -1;
-  }
+  const long v = sa::read_redo_counter(g_w4_redo_blocks, reset);
+  if (v < 0) return -1;
   const long d = sa_direct_redo_blocks_internal(reset);
-  return d < 0 ? -1 : (long)v + d;
+  return d < 0 ? -1 : v + d;
 }
 
 // InstanceNorm partial count: the small blocks' tiling (a large block writes its two halves)

@@ -57,9 +57,6 @@ __device__ __forceinline__ float xform(float v, const InXform &t, long bc, int d
   return v;
 }
 
-#ifndef SA_STATS_DPP
-#define SA_STATS_DPP 1   // the wave sums of block_stats on DPP (0: __shfl_xor butterfly)
-#endif
 // block partial sums of (x, x^2) over the tile for each of NC channels -> partial[bc][blk].
 // A thread's own values (at most TD of them) are summed in fp32, everything above in fp64.
 template <int NC>
@@ -68,19 +65,9 @@ __device__ __forceinline__ void block_stats(const float (&s)[NC], const float (&
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
-#if SA_STATS_DPP
-    // (DPP: the ds_bpermute butterfly is 12 dependent LDS round trips per channel)
+    // (the wave sums on DPP: a __shfl_xor / ds_bpermute butterfly is 12 dependent LDS round trips per channel)
     const double a = sa::wave_sum_dpp_lane63((double)s[c]), e = sa::wave_sum_dpp_lane63((double)q[c]);
     if (lane == 63) {
-#else
-    double a = (double)s[c], e = (double)q[c];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      a += __shfl_xor(a, o);
-      e += __shfl_xor(e, o);
-    }
-    if (lane == 0) {
-#endif
       red[(c * 4 + wv) * 2] = a;
       red[(c * 4 + wv) * 2 + 1] = e;
     }
@@ -214,6 +201,7 @@ __global__ __launch_bounds__(256) void conv3d_onehot_s2_kernel(OneHotVol v, int 
 
 // F(4,3) transforms (points 0, +-1, +-2, inf; the same B^T / A^T as conv2d_wino4.hip), for
 // correlation along one axis: out[i] = sum_k g[k] x[i + k] = A^T ((G g) . (B^T x))
+// (separate from conv2d_wino4.hip's bt6 / at6 on purpose: plain multiplies and adds under -ffp-contract=off here, explicit fmaf under fp contract(fast) there)
 __device__ __forceinline__ void bt6(const float x0, const float x1, const float x2, const float x3, const float x4,
                                     const float x5, float *o) {
   const float a = x4 - 4.0f * x2, b = x3 - 4.0f * x1, c = x4 - x2, e = x3 - x1;
@@ -409,9 +397,6 @@ __global__ __launch_bounds__(256) void conv3d_kernel(const float *__restrict__ i
 //   DMA    = the next channel's raw columns fetched by LDS-DMA (buffer_load_dword ... lds) into
 //            a [6 rows][LD planes][64 lanes] staging area instead of 2 x LD VGPRs per thread; each
 //            wave reads back only its own lanes' words, after its own vmcnt(0) in commit
-#ifndef SA_WD_BUF
-#define SA_WD_BUF 0   // 1: the staging loads as buffer loads (diagnostic: 8 -> 8 then needs 175 VGPRs)
-#endif
 //   COTT   = the conv's total output channels when a block computes COUT of them (COUT = 16 of
 //            32: the 32-channel stride-1 conv as two channel halves, blockIdx.z = (b, D tile, half))
 template <int CIN, int COUT, int NT, bool GATED, bool WL = false, bool PK = false, bool DMA = false, int COTT = 0>
@@ -503,15 +488,8 @@ __global__ __launch_bounds__(256) void conv3d_wd_kernel(const float *__restrict_
             asm volatile("" : "+s"(la));
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void *)(uintptr_t)la, 4,
                                                      (off + hc * W + wcl) * 4, 0, 0, 0);
-          } else if constexpr (SA_WD_BUF) {
-            // a buffer load at a 32-bit lane offset from the channel's base (no 64-bit address
-            // per load); the plane offset in a VGPR (SGPRs hold the weights)
-            const __amdgpu_buffer_rsrc_t rs =
-                __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(src), (short)0, D * hw * 4, 0x00020000);
-            int vo = (off + hc * W + wcl) * 4;
-            asm volatile("" : "+v"(vo));
-            pv[k][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, vo, 0, 0));
           } else {
+            // (as buffer loads at 32-bit lane offsets, a diagnostic since removed, 8 -> 8 needed 175 VGPRs)
             asm volatile("" : "+v"(off));   // plane offsets in VGPRs: SGPRs hold the weights
             pv[k][j] = colp[off];
           }

@@ -38,8 +38,7 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using sa::f32x4, sa::f16x8;
 
 constexpr float kWScale = 4096.0f;   // 2^12: weights -> f16 range
 

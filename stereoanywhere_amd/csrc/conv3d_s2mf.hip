@@ -23,8 +23,7 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+using sa::f32x4, sa::f16x8;
 
 constexpr float kS2WScale = 4096.0f;                  // 2^12: weights -> f16 range
 constexpr int S2_CIN = 16, S2_COUT = 32, S2_KS = 14;  // K-steps: 2 taps x 16 channels

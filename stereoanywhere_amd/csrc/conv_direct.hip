@@ -26,10 +26,7 @@
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
-using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
+using sa::f32x4, sa::f32x2, sa::f16x2, sa::f16x4;
 
 // Split products (SP, sa_conv_direct_split): the weights are f16 (hi, lo) pairs of w * 2^12 in
 // one dword each (sa_conv_direct_weights_split), the patch values are split in registers, and
@@ -453,13 +450,7 @@ extern "C" int sa_conv_direct_weights_split(const float *arranged, long n, void 
 }
 
 long sa_direct_redo_blocks_internal(int reset) {
-  unsigned v = 0;
-  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_direct_redo_blocks), sizeof v) != hipSuccess) return -1;
-  if (reset) {
-    const unsigned z = 0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_direct_redo_blocks), &z, sizeof z) != hipSuccess) return -1;
-  }
-  return v;
+  return sa::read_redo_counter(g_direct_redo_blocks, reset, /*sync=*/false);   // (the caller has synchronised)
 }
 
 extern "C" long sa_conv_direct_weights_size(int Cout, int Cin, int K, int S, int with_ds) {

@@ -42,7 +42,6 @@ __device__ __forceinline__ void c1_load_weights(const float *__restrict__ wt, co
 template <int NT, class Store>
 __device__ __forceinline__ void c1_mfma(const float (&f)[NT], const C1Weights<NT> &w, float *lds, int lane,
                                         Store &&store) {
-  using f32x4 = __attribute__((ext_vector_type(4))) float;
 #pragma unroll
   for (int k = 0; k < NT; ++k) lds[k * C1_PITCH + lane] = f[k];
   // (the wave's own LDS writes precede its reads: DS operations of a wave complete in order)

@@ -142,13 +142,6 @@ __device__ __forceinline__ void hist_add(unsigned *h, unsigned bin, bool count) 
 // Every pass streams the sample's keys from memory (L2-resident after the first) in chunks of
 // L1_CH keys per thread whose loads are all in flight together: one load at a time, the pass
 // would wait a round trip per key.
-#ifdef SA_LSQ_CLOCK   // phase timestamps of block 0 (diagnostic builds)
-__device__ long long g_lsq_clock[8];
-#define LSQ_STAMP(i) \
-  if (blockIdx.x == 0 && threadIdx.x == 0) g_lsq_clock[i] = __builtin_amdgcn_s_memrealtime()
-#else
-#define LSQ_STAMP(i)
-#endif
 constexpr int L1_BINS = 16384, L1_SHIFT = 17, L1_POOL = 16384, L1_SEG = 8, L1_CH = 16;
 // Bin 0 holds the exact zeros alone, bin b >= 1 the positive keys whose top bits are b - 1: the
 // relu'd zeros can be half of a sample (the model's synthetic-weight disparities; an edge's
@@ -272,7 +265,6 @@ __global__ __launch_bounds__(LSQ_THREADS) void lsq1_kernel(const float *__restri
   const int b = blockIdx.x;
   const float *md = mde + (long)b * n, *dd = disp + (long)b * n, *cd = conf + (long)b * n;
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  LSQ_STAMP(7);
 
   // ranks of torch.quantile(linear): rank = q * (n - 1) in fp32
   const float r_lo = q_lo * (float)(n - 1), r_hi = q_hi * (float)(n - 1);
@@ -282,11 +274,9 @@ __global__ __launch_bounds__(LSQ_THREADS) void lsq1_kernel(const float *__restri
   }
   for (int i = t; i < L1_BINS; i += LSQ_THREADS) hist[i] = 0u;
   __syncthreads();
-  LSQ_STAMP(0);
   // A: histogram of the top bits
   lsq_stream_keys(dd, n, [&](unsigned k, int, bool v) { hist_add(hist, bin_of(k), v); });
   __syncthreads();
-  LSQ_STAMP(1);
   {
     unsigned sacc = 0;
 #pragma unroll
@@ -339,7 +329,6 @@ __global__ __launch_bounds__(LSQ_THREADS) void lsq1_kernel(const float *__restri
     s_total = off;
   }
   __syncthreads();
-  LSQ_STAMP(2);
   const bool fall = s_fall != 0;
   unsigned lb[4];
   int lsrc[4];
@@ -415,7 +404,6 @@ __global__ __launch_bounds__(LSQ_THREADS) void lsq1_kernel(const float *__restri
       }
     }
     __syncthreads();
-  LSQ_STAMP(3);
     // C: the low 17 bits of each rank's key as a 9-bit and an 8-bit digit (seg reused as [4][512])
     if (t < 4) s_pre[t] = lb[t] ? (lb[t] - 1u) << L1_SHIFT : 0u;   // (a zero-bin rank: key 0, done)
     for (int pass = 0; pass < 2; ++pass) {
@@ -463,14 +451,12 @@ __global__ __launch_bounds__(LSQ_THREADS) void lsq1_kernel(const float *__restri
     __syncthreads();
     lsq_select_radix(dd, n, hist, s_pre, s_rem);
   }
-  LSQ_STAMP(4);
   if (t < 2) {
     const float r = t == 0 ? r_lo : r_hi;
     const float lo = __uint_as_float(s_pre[2 * t]), hi = __uint_as_float(s_pre[2 * t + 1]);
     qv[t] = lerp_ref(lo, hi, r - truncf(r));
   }
   __syncthreads();
-  LSQ_STAMP(5);
   const float qlo = qv[0], qhi = qv[1];
   if (!fall && zero_lo && qlo <= 0.0f) {   // the zeros are inside the band (d = 0 >= lo = 0)
     s11 += z11;
@@ -507,7 +493,6 @@ __global__ __launch_bounds__(LSQ_THREADS) void lsq1_kernel(const float *__restri
   s22 = block_sum(s22, red);
   t1 = block_sum(t1, red);
   t2 = block_sum(t2, red);
-  LSQ_STAMP(6);
   if (t == 0) {
     const double det = s11 * s22 - s12 * s12;
     double sc, sh;
@@ -821,9 +806,3 @@ extern "C" int sa_mono_scale_mirror(const float *m2, const float *m3, const floa
   mirror_kernel<<<nb, 256, 0, s>>>(sm2, sm3, dL, conf_l, H, W, in_bs, lrc_th, div, conf_th, npix, mirror, coords_x);
   return sa::check_launch("sa_mono_scale_mirror/mirror");
 }
-
-#ifdef SA_LSQ_CLOCK
-extern "C" int sa_lsq_clock_read(long long *out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lsq_clock), sizeof(long long) * 8) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -32,8 +32,7 @@
 
 namespace {
 
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using sa::f32x4, sa::f16x8;
 
 constexpr int MU_PX = 48, MU_THR = 192, MU_CO = 144, MU_MT = 3, MU_NT = 3;
 constexpr int MU_LG_PITCH = 60;   // floats per logit row: rows 4 apart start 48 banks apart
@@ -260,12 +259,5 @@ extern "C" int sa_mask_upsample(const float *x, long x_bs, int B, int Cin, int H
 }
 
 extern "C" long sa_mask_upsample_redo_blocks(int reset) {
-  if (hipDeviceSynchronize() != hipSuccess) return -1;
-  unsigned v = 0;
-  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_mu_redo_blocks), sizeof v) != hipSuccess) return -1;
-  if (reset) {
-    const unsigned z = 0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_mu_redo_blocks), &z, sizeof z) != hipSuccess) return -1;
-  }
-  return v;
+  return sa::read_redo_counter(g_mu_redo_blocks, reset);
 }

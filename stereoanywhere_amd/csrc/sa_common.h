@@ -11,6 +11,13 @@
 
 namespace sa {
 
+// clang vector types of the MFMA operands and the 8 / 16-byte memory accesses
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+using f32x2 = __attribute__((ext_vector_type(2))) float;
+using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
+using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+
 void set_error(const char *fmt, ...);
 
 // Event-bracketed timing (sa_timing_enable). begin/end are no-ops when disabled.
@@ -35,6 +42,20 @@ inline int check_launch(const char *what) {
     return SA_E_LAUNCH;
   }
   return SA_OK;
+}
+
+// A __device__ counter of the blocks a range guard recomputed (sa_split_redo_blocks and its kin):
+// its value, or -1 on a HIP error; `reset` zeroes it after the read.  `sync` waits for the device
+// first, so every launch so far has counted (tests and bench.py, outside timed regions).
+inline long read_redo_counter(const unsigned &counter, int reset, bool sync = true) {
+  if (sync && hipDeviceSynchronize() != hipSuccess) return -1;
+  unsigned v = 0;
+  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(counter), sizeof v) != hipSuccess) return -1;
+  if (reset) {
+    const unsigned z = 0;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(counter), &z, sizeof z) != hipSuccess) return -1;
+  }
+  return v;
 }
 
 #define SA_REQUIRE(cond, ...)          \

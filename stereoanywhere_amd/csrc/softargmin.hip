@@ -455,10 +455,6 @@ __device__ __forceinline__ void slice_one(const float *__restrict__ src, float (
   slice_reduce<NR, NC, CONF, RT>(x, red, colv, n, g, outL, outR, ob, w, lane, tid, rconf);
 }
 
-#ifndef SA_SAM_CONF_FIRST
-#define SA_SAM_CONF_FIRST 1   // 0: the disparity blocks first (the order before round 6's last change)
-#endif
-
 template <int NR, int NC>
 __global__ __launch_bounds__(1024) void sam_slice_kernel(const float *__restrict__ vd, const float *__restrict__ vc,
                                                          SGeo g, int n, float *dL, float *dR, float *cL, float *cR,
@@ -468,7 +464,7 @@ __global__ __launch_bounds__(1024) void sam_slice_kernel(const float *__restrict
   // with both volumes the confidence blocks (the costlier kind: a log2 per cell and side) take
   // grid row 0, which the dispatcher issues first: the cheaper disparity blocks fill the last
   // partial round of one-block-per-CU waves (1088 blocks at cfg2 = 4.25 rounds of 256 CUs)
-  const int conf = gridDim.y == 2 ? SA_SAM_CONF_FIRST ^ (int)blockIdx.y : y0 + (int)blockIdx.y;
+  const int conf = gridDim.y == 2 ? 1 ^ (int)blockIdx.y : y0 + (int)blockIdx.y;
   const int bh = blockIdx.x, b = bh / g.H, h = bh % g.H;
   const long so = (long)b * g.sb + (long)h * g.sh;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -482,10 +478,6 @@ __global__ __launch_bounds__(1024) void sam_slice_kernel(const float *__restrict
   else
     slice_one<NR, NC, false>(vd + so, red, colv, n, g, dL, dR, ob, w, lane, tid);
 }
-
-#ifndef SA_SAM_DIAG
-#define SA_SAM_DIAG 0   // timing diagnostics (wrong results): 1 loads only, 2 no loads (synthetic cells)
-#endif
 
 // sam_slice_kernel with 16-byte rows (n % 4 == 0, n <= 256, rows 16-byte aligned): lane L holds
 // columns 4L .. 4L + 3 of each of its wave's rows (one dwordx4 load per row instead of four
@@ -511,18 +503,8 @@ __global__ __launch_bounds__(1024) void sam_slice4_kernel(const float *__restric
 #pragma unroll
   for (int r = 0; r < NR; ++r) {
     const int k = w + 16 * r;
-    if (SA_SAM_DIAG == 2)
-      x[r] = (k < n && lv) ? f4{(float)(k ^ lane), (float)(k + lane), (float)(k - lane), (float)(k * 3 % 7)} : f4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    else
-      x[r] = (k < n && lv) ? *reinterpret_cast<const f4 *>(src + (long)k * g.sk + 4 * lane)
-                           : f4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  }
-  if (SA_SAM_DIAG == 1) {
-    float t = 0.f;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) t += x[r].x + x[r].y + x[r].z + x[r].w;
-    if (t == 1.2345f) outL[ob + lane] = t;
-    return;
+    x[r] = (k < n && lv) ? *reinterpret_cast<const f4 *>(src + (long)k * g.sk + 4 * lane)
+                         : f4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
   }
   // ---- right: per row k, softmax over j
   const float lw_r = g.log2W1;
