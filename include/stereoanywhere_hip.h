@@ -29,7 +29,8 @@ extern "C" {
  * that sa_abi_version() == SA_ABI_VERSION and that sa_struct_size(SA_STRUCT_*) equals its own
  * sizeof: the arrays of SaWinoProblem / SaGateEpilogue / SaResampleJob are read at the library's
  * stride, so a host built against another layout would hand over misread fields.
- *   9: sa_corr_lookup_backward / sa_corr_pyramid_backward / sa_corr_volume_backward (additive)
+ *   9: sa_corr_lookup_backward / sa_corr_pyramid_backward / sa_corr_volume_backward (additive);
+ *      later, still 9: sa_softargmin_conf_backward(_ws_size) / sa_convex_upsample_backward (additive)
  *   8: block_shape 7 of sa_conv2d_k3_wino4_multi_gate / sa_conv2d_k3_wino4_launch (additive)
  *   7: sa_feature_gates / SaFeatureGateJob added (additive: no earlier entry point changed)
  *   6: round 6 (the implicit-GEMM entry points removed; sa_struct_size, sa_conv3d_mf_get_planes)
@@ -163,6 +164,30 @@ int sa_softargmin_conf(const float *vol_disp, const float *vol_conf, int B, int 
  * 16-byte-row variant (n % 4 == 0, n <= 256, aligned rows; slower); for A/B runs and tests. */
 void sa_softargmin_set_one_pass(int on);
 int sa_softargmin_get_one_pass(void);
+
+/* Adjoint of sa_softargmin_conf (diffops_backward.hip): fp32 data and per-element arithmetic, fp64
+ * per-line statistics (E, S and the sum of p they are divided by); deterministic (no floating-point
+ * atomics, one fixed summation order per element, the same bits every run).  Volumes by strides as
+ * above (sj == 1 or sk == 1; any W1, W2 > 1).  g_dL [B,H,W1], g_dR [B,H,W2], g_cL [B,H,W1],
+ * g_cR [B,H,W2] are the upstream gradients of the four outputs, dense; a NULL gradient means that
+ * output was not used and its term is skipped.  With p the softmax over k of row (b,h,j),
+ * E = sum_k p_k k, q the softmax over j of column (b,h,k), E' = sum_j q_j j,
+ * a = log2(p + 1e-6) + p / ((p + 1e-6) ln 2), S = sum_k p_k a_k, and a', S' the same on q:
+ *   grad_vol_disp[j,k] = -g_dL[j] p_jk (k - E_j) + g_dR[k] q_jk (j - E'_k)
+ *   grad_vol_conf[j,k] =  g_cL[j] p_jk (a_jk - S_j) / log2(W2) + g_cR[k] q_jk (a'_jk - S'_k) / log2(W1)
+ * each in its volume's strides, every element (b,h,j,k) written.  A volume whose two gradients are
+ * both NULL is not read and its output is not touched (both pointers may be NULL).  The softmaxes are
+ * recomputed from the volume with the line maximum subtracted; ws is a caller's workspace of
+ * sa_softargmin_conf_backward_ws_size(B, H, W1, W2) bytes (-1: bad shape), 8-byte aligned, for the
+ * per-line statistics of the strided side (16 bytes per line and volume: max, 1 / sum e, fp64 E or
+ * S).  It is read and written only when that side has a gradient (g_dR or g_cR with sk == 1, g_dL or
+ * g_cL otherwise) and may be NULL when it has none.  sk == 1 (the reference's [B,1,H,W1,W2]) is the coalesced
+ * case that training passes.  Per volume: two reads and one write. */
+long sa_softargmin_conf_backward_ws_size(int B, int H, int W1, int W2);
+int sa_softargmin_conf_backward(const float *vol_disp, const float *vol_conf, int B, int H, int W1, int W2,
+                                long sb, long sh, long sj, long sk, const float *g_dL, const float *g_dR,
+                                const float *g_cL, const float *g_cR, float *grad_vol_disp,
+                                float *grad_vol_conf, void *ws, void *stream);
 
 /* a7 — softlrc (utils.py:189-198) with disp_warping (utils.py:172-187); optional
  * fuzzy_and with a confidence (utils.py:240-241, stereoanywhere.py:188-189):
@@ -335,6 +360,20 @@ int sa_corr_lookup_conv1x1_sheared(const float *sheared_a, const float *sheared_
  * flow_up, i.e. minus the disparity). */
 int sa_convex_upsample(const float *flow, const float *mask, long mask_bs, int B, int H, int W,
                        int factor, float *out, void *stream);
+
+/* Adjoint of convex_upflow with D = 1 (diffops_backward.hip): fp32 data and per-element arithmetic,
+ * grad_flow summed in an fp64 accumulator; deterministic.  flow [B,1,H,W],
+ * mask [B, 9*f*f, H, W] with batch stride mask_bs, grad_out [B,1,f*H,f*W], factor f = 1..8;
+ * scale = f with use_scale_factor, else 1.  Channel t*f*f + a*f + b of the mask belongs to tap t
+ * (flow[h + t/3 - 1, w + t%3 - 1], zero outside) of output pixel (h*f + a, w*f + b).  With s the
+ * softmax over t and u_t = scale * flow(tap t):
+ *   grad_mask[t,a,b,h,w] = s_t (u_t - sum_t' s_t' u_t') g[h f + a, w f + b]      (dense [B,9*f*f,H,W])
+ *   grad_flow[y,x] = scale * sum_t sum_a sum_b s_t(a,b,y',x') g[y' f + a, x' f + b],
+ *     (y',x') = (y,x) - (t/3 - 1, t%3 - 1) in range; a gather, summed t, then a, then b, ascending.
+ * Either output may be NULL to skip it (not both); flow may be NULL when grad_mask is. */
+int sa_convex_upsample_backward(const float *flow, const float *mask, long mask_bs, const float *grad_out,
+                                int B, int H, int W, int factor, float scale, float *grad_flow,
+                                float *grad_mask, void *stream);
 
 /* Mono hourglass (hourglass.py:13-91, submodule.py:25-53, 113-140) and its classifiers
  * (stereoanywhere.py:165-166) as fused direct 3-D convolutions on [B, C, D, H, W] volumes

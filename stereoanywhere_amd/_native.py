@@ -91,6 +91,9 @@ SIGNATURES = {
     "sa_softargmin_conf": (I, [P, P, I, I, I, I, L, L, L, L, P, P, P, P, L, P]),
     "sa_softargmin_set_one_pass": (None, [I]),
     "sa_softargmin_get_one_pass": (I, []),
+    "sa_softargmin_conf_backward_ws_size": (L, [I, I, I, I]),
+    "sa_softargmin_conf_backward": (I, [P, P, I, I, I, I, L, L, L, L, P, P, P, P, P, P, P, P]),
+    "sa_convex_upsample_backward": (I, [P, P, L, P, I, I, I, I, F, P, P, P]),
     "sa_split_redo_blocks": (L, [I]),
     "sa_conv2d_k3_wino4_launch": (I, [I, P, P, I, I, P]),
     "sa_flow_head_part_size": (L, [I, I, I, I]),

@@ -1,0 +1,179 @@
+"""Differentiable drop-ins for the reference's soft-argmin / entropy-confidence functions and its
+convex up-sampling (models/stereoanywhere/utils/utils.py:97-170).
+
+``estimate_left_disparity``, ``estimate_right_disparity``, ``estimate_left_confidence``,
+``estimate_right_confidence`` and ``convex_upflow`` keep the reference's names and signatures;
+``softargmin_conf`` is the joint form (all four maps of a disparity and a confidence volume from one
+forward and one backward) and the one to prefer: four separate calls are four forwards, four
+backwards and two volume-sized additions by autograd.
+
+With grad mode on and an input that requires grad the functions run as the autograd functions below:
+the forward is the inference kernel (``ops.softargmin_conf`` / ``ops.convex_upsample``, so the same
+bits), the backward a deterministic HIP adjoint (csrc/diffops_backward.hip) that recomputes the
+softmaxes from the saved inputs; nothing but the inputs is saved.  Otherwise they make the plain
+``ops`` calls and return tensors without a ``grad_fn``.  Double backward is not built.
+
+Floating inputs that are not fp32 (fp16 / bf16 activations under ``torch.autocast``) are cast with
+``.float()``: a torch op, so the gradient arrives at the caller's tensor in its own dtype.  There is
+no CPU path.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import ops
+from .corr import _wants_grad
+
+
+def _on_gpu(t: torch.Tensor, name: str) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.device.type != "cuda":
+        raise RuntimeError(f"{name} must be on the GPU (the HIP path has no CPU fallback), got {t.device}")
+    if not t.is_floating_point():
+        raise RuntimeError(f"{name} must be a floating-point tensor, got {t.dtype}")
+
+
+# ------------------------------------------------------------------------------- soft-argmin
+def _volume(v: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
+    """[B,1,H,W1,W2] in fp32 with W1 or W2 at stride 1 (a view where the input already is)."""
+    if v is None:
+        return None
+    _on_gpu(v, name)
+    if v.dim() != 5 or v.shape[1] != 1:
+        raise RuntimeError(f"{name} must be [B,1,H,W1,W2], got {tuple(v.shape)}")
+    if v.shape[3] < 2 or v.shape[4] < 2:
+        raise RuntimeError(f"{name}: W1 and W2 must be at least 2, got {tuple(v.shape)}")
+    v = v.float()
+    if v.stride(4) != 1 and v.stride(3) != 1:
+        v = v.contiguous()
+    return v
+
+
+def _geometry(v: torch.Tensor):
+    B, _, H, W1, W2 = v.shape
+    return (v.stride(0), v.stride(2), v.stride(3), v.stride(4)), (B, H, W1, W2)
+
+
+def _forward_maps(vol_disp, vol_conf):
+    """The inference kernel on either or both volumes -> (dL, dR, cL, cR), [B,1,H,W] each or None."""
+    strides, dims = _geometry(vol_disp if vol_disp is not None else vol_conf)
+    return ops.softargmin_conf_maps(vol_disp, vol_conf, strides, dims)
+
+
+class _SoftArgminConfFn(torch.autograd.Function):
+    """ops.softargmin_conf with ops.softargmin_conf_backward as its adjoint.  Saves the volumes only;
+    an output nobody used arrives as a None gradient and is passed on as a null pointer."""
+
+    @staticmethod
+    def forward(ctx, vol_disp, vol_conf):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(vol_disp, vol_conf)
+        return _forward_maps(vol_disp, vol_conf)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_dL, g_dR, g_cL, g_cR):
+        vol_disp, vol_conf = ctx.saved_tensors
+        need_d, need_c = ctx.needs_input_grad
+        if not need_d:
+            g_dL = g_dR = None
+        if not need_c:
+            g_cL = g_cR = None
+        grads = [None if g is None else g.float().contiguous() for g in (g_dL, g_dR, g_cL, g_cR)]
+        if all(g is None for g in grads):
+            return None, None
+        ref = vol_disp if vol_disp is not None else vol_conf
+        strides, dims = _geometry(ref)
+        return ops.softargmin_conf_backward(vol_disp, vol_conf, strides, dims, *grads)
+
+
+def softargmin_conf(vol_disp: Optional[torch.Tensor], vol_conf: Optional[torch.Tensor]):
+    """(estimate_left_disparity(vol_disp), estimate_right_disparity(vol_disp),
+    estimate_left_confidence(vol_conf), estimate_right_confidence(vol_conf)) from one forward and one
+    backward; volumes [B,1,H,W1,W2], either may be None (its two maps are None)."""
+    vol_disp, vol_conf = _volume(vol_disp, "vol_disp"), _volume(vol_conf, "vol_conf")
+    if vol_disp is None and vol_conf is None:
+        raise RuntimeError("softargmin_conf: both volumes are None")
+    if vol_disp is not None and vol_conf is not None:
+        if vol_disp.shape != vol_conf.shape:
+            raise RuntimeError(f"softargmin_conf: the volumes must have one shape, got {tuple(vol_disp.shape)} "
+                               f"and {tuple(vol_conf.shape)}")
+        if _geometry(vol_disp)[0] != _geometry(vol_conf)[0]:   # one set of strides per call
+            vol_disp, vol_conf = vol_disp.contiguous(), vol_conf.contiguous()
+    if _wants_grad(vol_disp, vol_conf):
+        return _SoftArgminConfFn.apply(vol_disp, vol_conf)
+    return _forward_maps(vol_disp, vol_conf)
+
+
+def _padded(x: torch.Tensor, vol_pad: Sequence[int]) -> torch.Tensor:
+    return x[:, :, :, vol_pad[0]:x.shape[3] - vol_pad[1]]
+
+
+def estimate_left_disparity(corr_volume, vol_pad=[0, 0]):
+    return _padded(softargmin_conf(corr_volume, None)[0], vol_pad)
+
+
+def estimate_right_disparity(corr_volume, vol_pad=[0, 0]):
+    return _padded(softargmin_conf(corr_volume, None)[1], vol_pad)
+
+
+def estimate_left_confidence(corr_volume, logsumexp_eps=1e-3):
+    return softargmin_conf(None, corr_volume)[2]
+
+
+def estimate_right_confidence(corr_volume, logsumexp_eps=1e-3):
+    return softargmin_conf(None, corr_volume)[3]
+
+
+# ------------------------------------------------------------------------- convex up-sampling
+class _ConvexUpFn(torch.autograd.Function):
+    """ops.convex_upsample with ops.convex_upsample_backward as its adjoint.  Saves flow and mask."""
+
+    @staticmethod
+    def forward(ctx, flow, mask, factor, use_scale_factor):
+        ctx.save_for_backward(flow, mask)
+        ctx.geo = (factor, float(factor) if use_scale_factor else 1.0)
+        return _upsample(flow, mask, factor, use_scale_factor)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        flow, mask = ctx.saved_tensors
+        factor, scale = ctx.geo
+        need_flow, need_mask = ctx.needs_input_grad[:2]
+        if not (need_flow or need_mask):
+            return None, None, None, None
+        g_flow, g_mask = ops.convex_upsample_backward(flow, mask, grad.float().contiguous(), factor, scale,
+                                                      need_flow, need_mask)
+        return g_flow, g_mask, None, None
+
+
+def _upsample(flow, mask, factor, use_scale_factor):
+    # the kernel multiplies the flow by the factor; without use_scale_factor it gets flow / factor
+    # (a power of two: both steps are exact)
+    return ops.convex_upsample(flow if use_scale_factor else flow * (1.0 / factor), mask, factor)
+
+
+def convex_upflow(flow, mask, n_downsample=2, use_scale_factor=True):
+    """The reference's convex_upflow for one flow channel: flow [N,1,H,W], mask [N,9*f*f,H,W],
+    f = 2**n_downsample <= 8 -> [N,1,f*H,f*W]."""
+    _on_gpu(flow, "flow")
+    _on_gpu(mask, "mask")
+    if flow.dim() != 4 or mask.dim() != 4:
+        raise RuntimeError(f"convex_upflow: flow and mask must be 4-D, got {tuple(flow.shape)} and {tuple(mask.shape)}")
+    n, d, h, w = flow.shape
+    if d != 1:
+        raise RuntimeError(f"convex_upflow: flow has D = {d} channels; the HIP path up-samples D == 1 (the x flow) only")
+    if not 0 <= n_downsample <= 3:
+        raise RuntimeError(f"convex_upflow: n_downsample must be 0..3 (factor 1..8), got {n_downsample}")
+    factor = 2 ** n_downsample
+    if tuple(mask.shape) != (n, 9 * factor * factor, h, w):
+        raise RuntimeError(f"convex_upflow: mask must be {(n, 9 * factor * factor, h, w)}, got {tuple(mask.shape)}")
+    flow, mask = flow.float().contiguous(), mask.float().contiguous()
+    if _wants_grad(flow, mask):
+        return _ConvexUpFn.apply(flow, mask, factor, bool(use_scale_factor))
+    return _upsample(flow, mask, factor, use_scale_factor)

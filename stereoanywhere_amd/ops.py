@@ -274,6 +274,81 @@ def corr_volume_backward(grad_volume: torch.Tensor, fmap2: torch.Tensor, fmap3: 
     return g2, g3
 
 
+def softargmin_conf_backward(vol_disp: Optional[torch.Tensor], vol_conf: Optional[torch.Tensor], strides, dims,
+                             g_dL: Optional[torch.Tensor] = None, g_dR: Optional[torch.Tensor] = None,
+                             g_cL: Optional[torch.Tensor] = None, g_cR: Optional[torch.Tensor] = None,
+                             out_disp: Optional[torch.Tensor] = None, out_conf: Optional[torch.Tensor] = None):
+    """Adjoint of softargmin_conf.  Volumes addressed as in softargmin_conf (dims (B, H, W1, W2), strides
+    (sb, sh, sj, sk)); g_dL / g_cL hold B*H*W1 floats, g_dR / g_cR B*H*W2, contiguous; None: that output
+    was not used.  -> (grad_vol_disp, grad_vol_conf), each laid out like its volume (``out_*``: a buffer
+    of the volume's shape and strides), None for a volume without an upstream gradient (its ``out_*``
+    is left as it is).  Deterministic."""
+    B, H, W1, W2 = dims
+    sb, sh, sj, sk = strides
+    grads = (g_dL, g_dR, g_cL, g_cR)
+    for name, t, n in zip(("g_dL", "g_dR", "g_cL", "g_cR"), grads, (W1, W2, W1, W2)):
+        if t is not None:
+            _check(t, name)
+            if t.numel() != B * H * n:
+                raise RuntimeError(f"{name} must hold B*H*W = {B * H * n} floats, got {tuple(t.shape)}")
+    use_d = g_dL is not None or g_dR is not None
+    use_c = g_cL is not None or g_cR is not None
+    if not (use_d or use_c):
+        raise RuntimeError("softargmin_conf_backward: nothing to compute (all four upstream gradients are None)")
+    outs = []
+    for name, use, vol, out in (("vol_disp", use_d, vol_disp, out_disp), ("vol_conf", use_c, vol_conf, out_conf)):
+        if not use:
+            outs.append(None)
+            continue
+        if vol is None:
+            raise RuntimeError(f"softargmin_conf_backward: {name} is None but its output has a gradient")
+        _check(vol, name, contiguous=False)
+        if out is None:
+            out = torch.empty_strided(vol.shape, vol.stride(), device=vol.device, dtype=torch.float32)
+        else:
+            _check(out, "out_" + name[4:], contiguous=False)
+            if out.shape != vol.shape or out.stride() != vol.stride():
+                raise RuntimeError(f"softargmin_conf_backward: out_{name[4:]} must have {name}'s shape and strides")
+        outs.append(out)
+    ref = next(t for t in grads if t is not None)
+    nbytes = N.lib().sa_softargmin_conf_backward_ws_size(B, H, W1, W2)
+    if nbytes < 0:
+        raise RuntimeError(f"softargmin_conf_backward: bad dims {tuple(dims)} (B, H > 0; W1, W2 > 1)")
+    # the workspace holds the statistics of the strided side: needed when that side has a gradient
+    strided = (g_dR, g_cR) if sk == 1 else (g_dL, g_cL)
+    ws = None
+    if any(t is not None for t in strided):
+        ws = torch.empty((nbytes // 4,), device=ref.device, dtype=torch.float32)
+    N.call("sa_softargmin_conf_backward", _ptr(vol_disp) if use_d else None, _ptr(vol_conf) if use_c else None,
+           B, H, W1, W2, sb, sh, sj, sk, _ptr(g_dL), _ptr(g_dR), _ptr(g_cL), _ptr(g_cR),
+           _ptr(outs[0] if use_d else out_disp), _ptr(outs[1] if use_c else out_conf), _ptr(ws), _stream(ref))
+    return outs[0], outs[1]
+
+
+def convex_upsample_backward(flow_x: torch.Tensor, mask: torch.Tensor, grad_out: torch.Tensor, factor: int = 4,
+                             scale: Optional[float] = None, need_flow: bool = True, need_mask: bool = True):
+    """Adjoint of convex_upsample: flow_x [B,1,H,W], mask [B,9*f*f,H,W], grad_out [B,1,f*H,f*W]
+    (contiguous) -> (grad_flow [B,1,H,W], grad_mask [B,9*f*f,H,W]); an output that is not needed is
+    None and is not computed.  scale: the factor the flow was multiplied by (default: ``factor``, the
+    reference's use_scale_factor=True; 1.0 without it).  Deterministic."""
+    _check(flow_x, "flow_x")
+    _check(grad_out, "grad_out")
+    B, _, H, W = flow_x.shape
+    mbs = _plane_bs(mask, "mask", mask.shape[1])
+    if flow_x.shape[1] != 1 or tuple(mask.shape) != (B, 9 * factor * factor, H, W):
+        raise RuntimeError(f"convex_upsample_backward: flow_x must be [B,1,H,W] and mask [B,{9 * factor * factor},H,W], "
+                           f"got {tuple(flow_x.shape)} and {tuple(mask.shape)}")
+    if tuple(grad_out.shape) != (B, 1, factor * H, factor * W):
+        raise RuntimeError(f"grad_out must be {(B, 1, factor * H, factor * W)}, got {tuple(grad_out.shape)}")
+    if not (need_flow or need_mask):
+        raise RuntimeError("convex_upsample_backward: nothing to compute")
+    g_flow = torch.empty_like(flow_x) if need_flow else None
+    g_mask = torch.empty(mask.shape, device=mask.device, dtype=torch.float32) if need_mask else None
+    N.call("sa_convex_upsample_backward", flow_x.data_ptr(), mask.data_ptr(), mbs, grad_out.data_ptr(), B, H, W,
+           factor, float(factor if scale is None else scale), _ptr(g_flow), _ptr(g_mask), _stream(flow_x))
+    return g_flow, g_mask
+
+
 def _lookup_bytes(npix: int, nvol: int, num_levels: int, radius: int, cout: int) -> float:
     """Algorithmic bytes of one fused lookup: per pixel the coordinate, per volume the 2r + 2 cells
     of each level's window and the cout output planes."""
@@ -430,6 +505,31 @@ def softargmin_conf(vol_disp: Optional[torch.Tensor], vol_conf: Optional[torch.T
     N.call("sa_softargmin_conf", _ptr(vol_disp), _ptr(vol_conf), B, H, W1, W2, sb, sh, sj, sk, dL, dR, cL, cR,
            obs, _stream(ref))
     return out_disp, out_conf
+
+
+def softargmin_conf_maps(vol_disp: Optional[torch.Tensor], vol_conf: Optional[torch.Tensor], strides, dims):
+    """softargmin_conf as four maps (dL [B,1,H,W1], dR [B,1,H,W2], cL, cR; None for a missing volume), for
+    any W1, W2.  With W1 == W2 they are the channels of softargmin_conf's joint buffers; otherwise the
+    left and right maps differ in width and each pair lives in one [2, B, H*max(W1, W2)] buffer (the
+    kernel takes one batch stride for all four maps), so the maps are not contiguous across the batch."""
+    B, H, W1, W2 = dims
+    if W1 == W2:
+        od, oc = softargmin_conf(vol_disp, vol_conf, strides, dims)
+        return (None if od is None else od[:, 0:1], None if od is None else od[:, 1:2],
+                None if oc is None else oc[:, 0:1], None if oc is None else oc[:, 1:2])
+    ref = vol_disp if vol_disp is not None else vol_conf
+    obs = H * max(W1, W2)
+
+    def pair(v):
+        if v is None:
+            return None, None
+        buf = torch.empty((2, B, obs), device=ref.device, dtype=torch.float32)
+        return buf[0, :, :H * W1].view(B, 1, H, W1), buf[1, :, :H * W2].view(B, 1, H, W2)
+    dL, dR = pair(vol_disp)
+    cL, cR = pair(vol_conf)
+    N.call("sa_softargmin_conf", _ptr(vol_disp), _ptr(vol_conf), B, H, W1, W2, *strides, _ptr(dL), _ptr(dR),
+           _ptr(cL), _ptr(cR), obs, _stream(ref))
+    return dL, dR, cL, cR
 
 
 # ----------------------------------------------------------------------- a7 + a8 + a11
