@@ -562,9 +562,12 @@ int sa_conv2d_k3_wino_multi(int nprob, const SaWinoProblem *probs, void *stream)
  * ([N*Cout][parts][2], parts = sa_conv2d_k3_wino4_stat_parts(H, W)) as sa_conv2d_k3_wino_ex. */
 int sa_conv2d_wino4_weights(const float *weight, int Cout, int Cin, float *U4, void *stream);
 /* U4 for the split block shape (block_shape 6 of sa_conv2d_k3_wino4_multi_gate: the Winograd-domain
- * products on f16 MFMA with hi/lo operand pairs): 36*Cin*Cout dwords in U4's layout, each dword
- * the f16 pair (hi, lo) of U * 2^12 (hi in the low half).  Needs |weight| < 16 (U * 2^12
- * within the f16 range). */
+ * products on f16 MFMA with hi/lo operand pairs): 36*Cin*Cout dwords, an opaque buffer.  Per
+ * filter value the f16 pair hi = f16(U * 2^12), lo = f16(U * 2^12 - hi), laid out as f16
+ * [Cout/32][Cin/8][36 points][4 k][16 n][2 groups][hi | lo][2 jobs] for input channel
+ * 8 chunk + 4 job + k and output channel 32 block + 16 group + n: one dword holds the hi halves of
+ * the two jobs (channels k and k + 4; job 0 in the low half), the next dword their lo halves.  Needs
+ * |weight| < 16 (U * 2^12 within the f16 range). */
 int sa_conv2d_wino4_weights_split(const float *weight, int Cout, int Cin, void *U4s, void *stream);
 long sa_conv2d_k3_wino4_stat_parts(int H, int W);
 int sa_conv2d_k3_wino4_multi(int nprob, const SaWinoProblem *probs, void *stream);

@@ -77,13 +77,15 @@ using W4Big = W4Cfg<8, 8>;
 using W4Small = W4Cfg<4, 4>;
 // Split: the 8-wave shape whose Winograd-domain products run on v_mfma_f32_16x16x16_f16 instead of
 // v_mfma_f32_16x16x4_f32.  Each operand is an f16 hi/lo pair (x = hi + lo, 22 significant bits;
-// filters scaled by 2^W4S_LOG2 before the split and the accumulators by 2^-W4S_LOG2 after the main
-// loop, both exact), and one MFMA's K = 16 slots hold a lane's channel as the four products
-// hi*bhi + hi*blo + lo*bhi + lo*blo: the A operand (hi, hi, lo, lo) is the lane's transformed value
-// (3 VALU to split), the B operand (bhi, blo, bhi, blo) is the filter's (bhi, blo) dword twice: the
-// LDS image holds each pair once (sa_conv2d_wino4_weights_split; the same bytes per chunk as the
-// fp32 filters, so the same L2 -> LDS intake per channel, which bounds this kernel family), one
-// ds_read_b64 gives a lane both output-channel groups' pairs, and the copy is a register move.
+// filters scaled by 2^W4S_LOG2 before the split and the finished sums by 2^-W4S_LOG2 in the
+// epilogue's last FMA, both exact), and one MFMA pair's K = 16 slots hold a lane's two channels
+// (c and c + 4) as the products hi*bhi + hi*blo + lo*bhi of each: the A operands (hi0, hi1, hi0, hi1)
+// and (lo0, lo1, 0, 0) are the lane's two transformed values (5 VALU to split the pair,
+// w4_pair_split), the B operand (bhi0, bhi1, blo0, blo1) is two adjacent dwords of the LDS image as
+// they stand (sa_conv2d_wino4_weights_split: each pair once, the same bytes per chunk as the fp32
+// filters, so the same L2 -> LDS intake per channel, which bounds this kernel family; one
+// ds_read_b128 gives a lane both output-channel groups' operands of a point).
+// Main loop per chunk and wave: 250 VALU per 72 MFMAs (144 transform, 90 split, 16 other).
 // Products of f16 pairs are exact in fp32, so the result differs from the fp32 kernel only by the
 // operands' rounding (<= 2^-22 relative; below 2^-14 the lo halves are subnormal, an absolute
 // 2^-25) and the accumulation order.  |V| must stay below 65504 (the f16 range): V = B^T d B grows
@@ -93,8 +95,8 @@ constexpr int W4S_LOG2 = 12;
 // Half (block_shape 7, the mixed-precision mode): the split kernel with the Winograd-domain input
 // as ONE f16, hi = f16(V) (relative rounding 2^-11 per transformed value); the lo half, its two
 // converts, its v_fma_mix and its MFMA per (row, group) are gone.  The filters stay the exact
-// (bhi, blo) pairs of the same LDS image: the paired A operand (hi0, hi0, hi1, hi1) against
-// B = (bhi0, blo0, bhi1, blo1) gives hi0 (bhi0 + blo0) + hi1 (bhi1 + blo1) in fp32.  Scaling, range
+// (bhi, blo) pairs of the same LDS image: the paired A operand (hi0, hi1, hi0, hi1) against
+// B = (bhi0, bhi1, blo0, blo1) gives hi0 (bhi0 + blo0) + hi1 (bhi1 + blo1) in fp32.  Scaling, range
 // guard (an overflowed hi is +-inf: the staged sums turn non-finite), output transform and
 // epilogues are the split kernel's.  A config type of its own, not a W4Cfg parameter: the split
 // instances keep their names.
@@ -182,30 +184,43 @@ struct W4Launch {
 // The two channels of a lane's jobs (c and c + 4) as the A operands of one MFMA pair: hi = f16(x),
 // lo = f16(x - hi) (x - hi is exact in fp32; one v_fma_mix_f32 reads hi as f16), both
 // round-to-nearest-even;
-// ahi = (hi0, hi0, hi1, hi1), alo = (lo0, 0, lo1, 0) against B = (bhi0, blo0, bhi1, blo1), the two
-// channels' filter (hi, lo) dwords of one output channel, adjacent in the job-innermost LDS image
-// (one ds_read_b128 per point holds both groups' pairs): ahi . B = hi0 bhi0 + hi0 blo0 + hi1 bhi1 +
-// hi1 blo1, alo . B = lo0 bhi0 + lo1 bhi1,
+// ahi = (hi0, hi1, hi0, hi1), alo = (lo0, lo1, 0, 0) against B = (bhi0, bhi1, blo0, blo1), the two
+// channels' filter hi dword and lo dword of one output channel, adjacent in the LDS image
+// (wino4s_weights_kernel; one ds_read_b128 per point holds both groups' operands): ahi . B = hi0 bhi0 +
+// hi1 bhi1 + hi0 blo0 + hi1 blo1, alo . B = lo0 bhi0 + lo1 bhi1,
 // i.e. per channel hi*bhi + hi*blo + lo*bhi (the dropped lo*lo term is below 2^-22 of the product).
-// The B operand needs no register copy (the one-channel form duplicates the (bhi, blo) dword: one
-// v_mov per MFMA, ~1 of the kernel's 5-7 VALU per MFMA) at the same MFMA and LDS instruction counts.
+// 5 VALU per channel pair: one packed convert gives both hi halves, its copy the second dword of ahi,
+// the two residuals read the pair's halves through op_sel, and one packed convert gives both lo
+// halves.  Only the low dword of alo is written: its zero dword is the caller's, made once per block
+// (w4_alo_init), not once per value.  Neither operand of the MFMAs needs any other register copy.
 __device__ __forceinline__ void w4_pair_split(const float x0, const float x1, f16x4 &ahi, f16x4 &alo) {
-  const f16x2 h0 = __builtin_convertvector(f32x2{x0, x0}, f16x2);
-  const f16x2 h1 = __builtin_convertvector(f32x2{x1, x1}, f16x2);
+  const f16x2 p = __builtin_convertvector(f32x2{x0, x1}, f16x2);
+  const unsigned pu = __builtin_bit_cast(unsigned, p);
   float l0, l1;
-  asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(__builtin_bit_cast(unsigned, h0)), "v"(x0));
-  asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(__builtin_bit_cast(unsigned, h1)), "v"(x1));
-  const f16x2 q0 = __builtin_convertvector(f32x2{l0, 0.0f}, f16x2);
-  const f16x2 q1 = __builtin_convertvector(f32x2{l1, 0.0f}, f16x2);
-  ahi = __builtin_shufflevector(h0, h1, 0, 1, 2, 3);
-  alo = __builtin_shufflevector(q0, q1, 0, 1, 2, 3);
+  asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l0) : "v"(pu), "v"(x0));
+  asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(l1) : "v"(pu), "v"(x1));
+  const f16x2 q = __builtin_convertvector(f32x2{l0, l1}, f16x2);
+  ahi = __builtin_shufflevector(p, p, 0, 1, 0, 1);
+  alo = __builtin_shufflevector(q, __builtin_shufflevector(alo, alo, 2, 3), 0, 1, 2, 3);
+}
+// The alo operands' registers: N pairs used in rotation (a pair is rewritten only after the MFMAs
+// that read it N values earlier have issued), whose upper dword is zero for the whole block.
+// The zero goes through an empty asm so that the compiler keeps it in the pair instead of making it
+// again beside every converted value.
+template <int N>
+__device__ __forceinline__ void w4_alo_init(f16x4 (&ring)[N]) {
+#pragma unroll
+  for (int r = 0; r < N; ++r) {
+    unsigned z = 0;
+    asm volatile("" : "+v"(z));
+    ring[r] = __builtin_bit_cast(f16x4, f32x2{__builtin_bit_cast(float, z), __builtin_bit_cast(float, z)});
+  }
 }
 
-// The half kernel's A operand of a lane's two channels: (hi0, hi0, hi1, hi1), round-to-nearest-even
+// The half kernel's A operand of a lane's two channels: (hi0, hi1, hi0, hi1), round-to-nearest-even
 __device__ __forceinline__ f16x4 w4_pair_half(const float x0, const float x1) {
-  const f16x2 h0 = __builtin_convertvector(f32x2{x0, x0}, f16x2);
-  const f16x2 h1 = __builtin_convertvector(f32x2{x1, x1}, f16x2);
-  return __builtin_shufflevector(h0, h1, 0, 1, 2, 3);
+  const f16x2 p = __builtin_convertvector(f32x2{x0, x1}, f16x2);
+  return __builtin_shufflevector(p, p, 0, 1, 0, 1);
 }
 
 // Range guard of the split kernel: blocks whose f16 operands overflowed (|V| >= 65520 turns hi
@@ -687,7 +702,7 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
   int PSv = PS, PGv = PG;
   asm volatile("" : "+s"(PSv), "+s"(PGv));
   const int pread = k * PSv * 4 + 4 * trow * PGv * 4 + 4 * tcol + 2;
-  const int uread = (k * 16 + m) * CG * (SPLIT ? JPC : 1);   // (split: [k][n][g][job], wino4s_weights_kernel)
+  const int uread = (k * 16 + m) * CG * (SPLIT ? JPC : 1);   // (split: dwords [k][n][g][hi | lo], wino4s_weights_kernel)
 
   // acc[i][jj][g]: point (row i, column 3 HF + jj) of output-channel group g
   f32x4 acc[NR][3][CG];
@@ -723,6 +738,11 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
     }
     __syncthreads();
   }
+  // (w4_pair_split's lo operands: two register pairs in rotation; one in the affine-input instance,
+  // which with two spills 32 B per lane instead of 24, and with three 36 B and the plain instance 8 B)
+  constexpr int W4_ALO = AFF ? 1 : 2;
+  f16x4 alo_ring[W4_ALO];
+  if constexpr (W4Paired<C, AFF> && !HALF) w4_alo_init(alo_ring);
 #pragma unroll 1
   for (int kc = 0; kc < nchunks; ++kc) {
     const int cur = kc & 1;
@@ -777,17 +797,16 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
         rc[r] = *reinterpret_cast<const f32x2 *>(p + r * PGv * 4 + 6);
       }
     };
-    f32xg bc[NR], bn[NR];
+    f32xg bc[NR], bn[NR];   // (the fp32 kernels' unpaired loop)
     auto load_b = [&](int s, int jj, f32xg *b) __attribute__((always_inline)) {
 #pragma unroll
-      for (int i = 0; i < NR; ++i) {
-        if constexpr (SPLIT) {   // (the job's dwords of both groups: one ds_read2_b32)
-          const float *q = ub + (6 * i + 3 * HF + jj) * JPC * SB + s;
-          b[i] = f32xg{q[0], q[JPC]};
-        } else {
-          b[i] = *reinterpret_cast<const f32xg *>(ub + ((6 * i + 3 * HF + jj) * JPC + s) * SB);
-        }
-      }
+      for (int i = 0; i < NR; ++i) b[i] = *reinterpret_cast<const f32xg *>(ub + ((6 * i + 3 * HF + jj) * JPC + s) * SB);
+    };
+    // split: a point's operands of both groups, both jobs' hi halves and lo halves (one ds_read_b128)
+    f32x4 pc_[NR];   // (group 0: both jobs' hi, both jobs' lo; group 1: the same)
+    auto load_bp = [&](int jj, int i0, int i1) __attribute__((always_inline)) {
+#pragma unroll
+      for (int i = i0; i < i1; ++i) pc_[i] = *reinterpret_cast<const f32x4 *>(ub + (6 * i + 3 * HF + jj) * JPC * SB);
     };
     if constexpr (W4Paired<C, AFF>) {
       // both jobs' row passes first, then per column both jobs' column passes feed one MFMA pair per
@@ -800,25 +819,20 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
       load_rows(1, 0, 6);
 #pragma unroll
       for (int r = 0; r < 6; ++r) bt6h<HF>(ra[r].y, rb[r].x, rb[r].y, rb[r].z, rb[r].w, rc[r].x, t1[r]);
-      f32x4 pc_[NR];   // (group 0: job 0, job 1; group 1: job 0, job 1)
-      auto load_bp = [&](int jj, int i0, int i1, f32x4 (&b)[NR]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = i0; i < i1; ++i) b[i] = *reinterpret_cast<const f32x4 *>(ub + (6 * i + 3 * HF + jj) * JPC * SB);
-      };
 #pragma unroll
       for (int jj = 0; jj < 3; ++jj) {
         if (kc + 1 < nchunks) {
           issue_part(kc + 1, cur ^ 1, jj);
           __builtin_amdgcn_sched_barrier(0);
         }
-        load_bp(jj, 0, NR / 2, pc_);   // (rows 0-2 under the column passes, 3-5 under rows 0-2's MFMAs:
+        load_bp(jj, 0, NR / 2);   // (rows 0-2 under the column passes, 3-5 under rows 0-2's MFMAs:
                                        // a whole column at once, or the next column's, spills)
         float v0[6], v1[6];
         bt6(t0[0][jj], t0[1][jj], t0[2][jj], t0[3][jj], t0[4][jj], t0[5][jj], v0);
         bt6(t1[0][jj], t1[1][jj], t1[2][jj], t1[3][jj], t1[4][jj], t1[5][jj], v1);
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
-          if (i == 1) load_bp(jj, NR / 2, NR, pc_);
+          if (i == 1) load_bp(jj, NR / 2, NR);
           if constexpr (HALF) {   // one f16 per value: one MFMA per (row, group)
             const f16x4 ahi = w4_pair_half(v0[i], v1[i]);
 #pragma unroll
@@ -827,7 +841,9 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
               acc[i][jj][g] = __builtin_amdgcn_mfma_f32_16x16x16f16(ahi, bp, acc[i][jj][g], 0, 0, 0);
             }
           } else {
-            f16x4 ahi, alo;
+            f16x4 ahi;
+            f16x4 &alo = alo_ring[(NR * jj + i) % W4_ALO];
+            static_assert(3 * NR % W4_ALO == 0, "the rotation closes over a chunk");
             w4_pair_split(v0[i], v1[i], ahi, alo);
 #pragma unroll
             for (int g = 0; g < CG; ++g) {
@@ -841,7 +857,7 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
       }
     } else {
       load_rows(0, 0, 6);
-      load_b(0, 0, bc);
+      if constexpr (!SPLIT) load_b(0, 0, bc);
 #pragma unroll
       for (int s = 0; s < JPC; ++s) {
         if (s == 1) load_rows(1, 3, 6);
@@ -858,7 +874,9 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
             issue_part(kc + 1, cur ^ 1, jj);
             __builtin_amdgcn_sched_barrier(0);
           }
-          if (s + 1 < JPC || jj < 2) load_b(jj < 2 ? s : s + 1, jj < 2 ? jj + 1 : 0, bn);
+          // (split: one buffer, read per column as in the paired loop; a second one spills)
+          if constexpr (SPLIT) load_bp(jj, 0, NR / 2);
+          else if (s + 1 < JPC || jj < 2) load_b(jj < 2 ? s : s + 1, jj < 2 ? jj + 1 : 0, bn);
           float v[6];
           bt6(t[0][jj], t[1][jj], t[2][jj], t[3][jj], t[4][jj], t[5][jj], v);
           if constexpr (SPLIT) {
@@ -866,11 +884,15 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
             static_assert(HALF, "an unpaired split config is the half config");
 #pragma unroll
             for (int i = 0; i < NR; ++i) {
-              // (hi, hi, 0, 0) against the duplicated (bhi, blo) dword
-              const f16x4 a = __builtin_shufflevector(__builtin_convertvector(f32x2{v[i], v[i]}, f16x2),
-                                                      f16x2{(_Float16)0.0f, (_Float16)0.0f}, 0, 1, 2, 3);
-              const f16x4 b0 = __builtin_bit_cast(f16x4, f32x2{bc[i][0], bc[i][0]});
-              const f16x4 b1 = __builtin_bit_cast(f16x4, f32x2{bc[i][1], bc[i][1]});
+              if (i == 1) load_bp(jj, NR / 2, NR);
+              // job 0: (hi, 0, hi, 0), job 1: (0, hi, 0, hi) against the image's (bhi0, bhi1, blo0, blo1)
+              // as it stands: one convert and one copy per value, none per filter operand
+              const f16x2 h = __builtin_convertvector(s == 0 ? f32x2{v[i], 0.0f} : f32x2{0.0f, v[i]}, f16x2);
+              const f16x4 a = __builtin_shufflevector(h, h, 0, 1, 0, 1);
+              // (copies first: __builtin_bit_cast of the swizzle itself reads the vector's first bytes)
+              const f32x2 g0 = pc_[i].xy, g1 = pc_[i].zw;
+              const f16x4 b0 = __builtin_bit_cast(f16x4, g0);
+              const f16x4 b1 = __builtin_bit_cast(f16x4, g1);
               acc[i][jj][0] = __builtin_amdgcn_mfma_f32_16x16x16f16(a, b0, acc[i][jj][0], 0, 0, 0);
               acc[i][jj][1] = __builtin_amdgcn_mfma_f32_16x16x16f16(a, b1, acc[i][jj][1], 0, 0, 0);
             }
@@ -884,22 +906,19 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
           }
           __builtin_amdgcn_sched_barrier(0);   // bound the scheduler's hoisting (register pressure)
 
+          if constexpr (!SPLIT) {
 #pragma unroll
-          for (int i = 0; i < NR; ++i) bc[i] = bn[i];
+            for (int i = 0; i < NR; ++i) bc[i] = bn[i];
+          }
         }
       }
     }
   }
   __syncthreads();
-  if constexpr (SPLIT) {   // the filters' 2^W4S_LOG2 and the inputs' xscale (exact)
-    const float inv_scale = 1.0f / ((float)(1 << W4S_LOG2) * xscale);
-#pragma unroll
-    for (int i = 0; i < NR; ++i)
-#pragma unroll
-      for (int jj = 0; jj < 3; ++jj)
-#pragma unroll
-        for (int g = 0; g < CG; ++g) acc[i][jj][g] *= inv_scale;
-  }
+  // Split: the accumulators carry the filters' 2^W4S_LOG2 and the inputs' xscale.  A power of two
+  // commutes with the linear output transform, so the scale is applied once, in the finishing FMA of
+  // phase 1 below (the staged partials of phase 0 stay unscaled): no pass over the 144 accumulators.
+  const float inv_scale = SPLIT ? 1.0f / ((float)(1 << W4S_LOG2) * xscale) : 1.0f;
 
   // ---- output transform.  Lane holds tiles tg * 16 + 4 (lane >> 4) + i of output channels
   // g * 16 + (lane & 15), points of columns 3 HF .. 3 HF + 2.  Y = A^T M A: the column-wise
@@ -944,8 +963,14 @@ __device__ __forceinline__ bool w4_body(const W4Prob &P, const W4Gate *gate, con
           *o = y;
         } else {
           // half 1's partial + half 0's: (p1 + p0) + bias for either finishing half
-          f32x4 v = (HF == 0 ? (*o + y) : (y + *o)) + bv;
-          if constexpr (SPLIT) chk += v;   // (the range guard, before the ReLU that would mask a NaN)
+          f32x4 v = HF == 0 ? (*o + y) : (y + *o);
+          if constexpr (SPLIT) {   // (exact scale: the same bits as scaling before the transform)
+            v = f32x4{fmaf(v.x, inv_scale, bv), fmaf(v.y, inv_scale, bv), fmaf(v.z, inv_scale, bv),
+                      fmaf(v.w, inv_scale, bv)};
+            chk += v;   // (the range guard, before the ReLU that would mask a NaN)
+          } else {
+            v = v + bv;
+          }
           if (relu) v = f32x4{fmaxf(v.x, 0.0f), fmaxf(v.y, 0.0f), fmaxf(v.z, 0.0f), fmaxf(v.w, 0.0f)};
           *o = v;
         }
@@ -1064,11 +1089,12 @@ __global__ __launch_bounds__(256) void wino4_weights_kernel(const float *__restr
 }
 
 // Filters of the split kernel (W4Split): U = G g G^T in fp64, times 2^W4S_LOG2, as the f16
-// pair hi = f16(u), lo = f16(u - hi) in one dword (hi in the low half); per (32-channel block,
-// 8-channel chunk, point) [k][n][g][job]: a lane's four operands of a point (both groups, both
-// jobs' channels k and k + 4) are one 16-byte LDS read, the MFMA pairs' B operands as they stand.
+// pair hi = f16(u), lo = f16(u - hi); per (32-channel block, 8-channel chunk, point)
+// [k][n][g][hi | lo][job] in f16: one dword holds the hi halves of the two jobs' channels k and
+// k + 4 (job 0 in the low half), the next dword their lo halves.  A lane's eight operands of a point
+// (both groups) are one 16-byte LDS read, the MFMA pairs' B operands as they stand (w4_pair_split).
 __global__ __launch_bounds__(256) void wino4s_weights_kernel(const float *__restrict__ w, int Cout, int Cin,
-                                                             unsigned *__restrict__ U) {
+                                                             unsigned short *__restrict__ U) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)Cout * Cin) return;
   const int co = (int)(i / Cin), ci = (int)(i % Cin);
@@ -1088,10 +1114,10 @@ __global__ __launch_bounds__(256) void wino4s_weights_kernel(const float *__rest
       const double u = (t[a][0] * G[b][0] + t[a][1] * G[b][1] + t[a][2] * G[b][2]) * (double)(1 << W4S_LOG2);
       const _Float16 hi = (_Float16)(float)u;
       const _Float16 lo = (_Float16)(float)(u - (double)hi);
-      const unsigned pr = (unsigned)__builtin_bit_cast(unsigned short, hi) |
-                          ((unsigned)__builtin_bit_cast(unsigned short, lo) << 16);
       const int pt = 6 * a + b;
-      U[((((((long)cb * (Cin / 8) + chunk) * NPT + pt) * 4 + k) * 16 + n) * 2 + gg) * 2 + s] = pr;
+      unsigned short *q = U + (((((((long)cb * (Cin / 8) + chunk) * NPT + pt) * 4 + k) * 16 + n) * 2 + gg) * 4 + s);
+      q[0] = __builtin_bit_cast(unsigned short, hi);
+      q[2] = __builtin_bit_cast(unsigned short, lo);
     }
 }
 
@@ -1183,7 +1209,7 @@ extern "C" int sa_conv2d_wino4_weights_split(const float *weight, int Cout, int 
              "sa_conv2d_wino4_weights_split: bad arguments (Cin %% 8, Cout %% 32)");
   const long n = (long)Cout * Cin;
   hipStream_t s = sa::as_stream(stream);
-  wino4s_weights_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(weight, Cout, Cin, static_cast<unsigned *>(U));
+  wino4s_weights_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(weight, Cout, Cin, static_cast<unsigned short *>(U));
   return sa::check_launch("sa_conv2d_wino4_weights_split");
 }
 
