@@ -30,7 +30,8 @@ extern "C" {
  * sizeof: the arrays of SaWinoProblem / SaGateEpilogue / SaResampleJob are read at the library's
  * stride, so a host built against another layout would hand over misread fields.
  *   9: sa_corr_lookup_backward / sa_corr_pyramid_backward / sa_corr_volume_backward (additive);
- *      later, still 9: sa_softargmin_conf_backward(_ws_size) / sa_convex_upsample_backward (additive)
+ *      later, still 9: sa_softargmin_conf_backward(_ws_size) / sa_convex_upsample_backward (additive);
+ *      sa_softlrc_backward(_ws_size) / sa_weighted_lsq_stats / sa_weighted_lsq_backward (additive)
  *   8: block_shape 7 of sa_conv2d_k3_wino4_multi_gate / sa_conv2d_k3_wino4_launch (additive)
  *   7: sa_feature_gates / SaFeatureGateJob added (additive: no earlier entry point changed)
  *   6: round 6 (the implicit-GEMM entry points removed; sa_struct_size, sa_conv3d_mf_get_planes)
@@ -209,6 +210,70 @@ int sa_weighted_lsq(const float *mde, const float *disp, const float *conf, int 
 long sa_weighted_lsq_ws_size(int B, int n_per_b);
 int sa_weighted_lsq_ws(const float *mde, const float *disp, const float *conf, int B, int n_per_b,
                        float q_lo, float q_hi, float *scale, float *shift, void *ws, void *stream);
+
+/* Adjoint of sa_softlrc (lsq_backward.hip), its fused conf2 / conf3 product included: fp32 data, each
+ * output element formed in fp64 and rounded once; deterministic (no floating-point atomics, one fixed
+ * summation order per element, the same bits every run).  The cell (floor(ix), floor(iy)) and its bounds
+ * are the ones the forward's fp32 arithmetic picks; the weights within it are fp64.  d2, d3, conf2, conf3 (either confidence may be NULL), B, H, W, map_bs, lrc_th as the forward
+ * takes them; g_s2, g_s3: the upstream gradients of s2 and s3 in the same layout, NULL: that output was
+ * not used (at least one is given).  For the left map, with r = relu(d2[y,x]),
+ *   ix = ((x - r) / W) (W - 1),  iy = (y / H) (H - 1)      (the reference divides by W and H under
+ *                                                           align_corners=True; kept)
+ *   S = the bilinear sample of d3 at (ix, iy) with zero padding (taps floor(ix), floor(ix) + 1 and
+ *       floor(iy), floor(iy) + 1; a tap outside the plane contributes 0),
+ *   u = d2[y,x] - S,  z = lrc_th - |u|,  v = softplus(z) / div,  div = log(1 + exp(lrc_th)),
+ *   s2 = v (conf2 ? conf2 : 1),
+ * and the right map is the mirror image: r = relu(d3), ix from x + r, S sampled from d2.  With
+ * t = g_s2 (conf2 ? conf2 : 1) dv/du and dv/du = -sigmoid(z) sign(u) / div (sign(0) = 0; 1 in place
+ * of sigmoid(z) for z > 20, softplus's threshold):
+ *   grad_conf2[y,x] = g_s2 v
+ *   grad_d2[y,x]    = t (1 + dS/dix (W - 1) / W [d2 > 0])        (relu'(0) = 0; dS/dix from the
+ *                                                                 taps inside the plane only)
+ *                     + sum over the right map's pixels p whose taps land on (y,x) of -t_p weight_p
+ * and likewise for grad_d3 with dix/dd3 = +(W - 1) / W, i.e. t (1 - dS/dix (W - 1) / W [d3 > 0]).  The
+ * last sum is a gather: pixel (y,x) scans the source rows whose two tap rows can include y (rows
+ * y - 1 .. y + 1, W pixels each) ascending in row, then column, into one accumulator.
+ * Every output pointer may be NULL (not computed); every element of a requested output is written
+ * (zeros where the map's upstream gradient is NULL).  grad_conf2 needs conf2, grad_conf3 conf3.  ws: a
+ * caller's workspace of sa_softlrc_backward_ws_size(B, H, W) bytes (-1: bad shape; four [B,H,W] fp64
+ * maps: t and the own term of either side), 8-byte aligned, written by the first launch and read by
+ * the gather; required when a map's gradient is requested and the other map's output has an upstream
+ * gradient (grad_d2 with g_s3, grad_d3 with g_s2), otherwise it may be NULL. */
+long sa_softlrc_backward_ws_size(int B, int H, int W);
+int sa_softlrc_backward(const float *d2, const float *d3, const float *conf2, const float *conf3, int B,
+                        int H, int W, long map_bs, float lrc_th, const float *g_s2, const float *g_s3,
+                        float *grad_d2, float *grad_d3, float *grad_conf2, float *grad_conf3, void *ws,
+                        void *stream);
+
+/* sa_weighted_lsq (the one-launch form: the same kernel, a second instantiation; scale and shift
+ * are the same bits) plus the sample's record for sa_weighted_lsq_backward: rec[b * SA_LSQ_REC + i],
+ * doubles, 8-byte aligned,
+ *   0..2  s11, s12, s22: the fp64 normal-equation sums over the band, sum of (|m| w)^2, (|m| w) w and
+ *         w^2 with w = sqrt(0.9 |c| + 0.1) (fp32 products, fp64 sums)
+ *   3, 4  lo, hi: the two fp32 band thresholds relu(disp) was compared against (exact in a double)
+ *   5     0: full rank; 1: rank-deficient (every kept |m| equal: the minimum-norm branch);
+ *         2: empty band. */
+#define SA_LSQ_REC 6
+int sa_weighted_lsq_stats(const float *mde, const float *disp, const float *conf, int B, int n_per_b,
+                          float q_lo, float q_hi, float *scale, float *shift, double *rec, void *stream);
+
+/* Adjoint of sa_weighted_lsq_stats, element-wise over the [B, n_per_b] maps; fp32 data, the per-sample
+ * 2x2 solve and each element's arithmetic in fp64, rounded once; deterministic.  g_scale,
+ * g_shift [B]: the upstream gradients, either may be NULL (taken as 0; at least one is given).  Per
+ * sample, with a = |mde|, y = relu(disp), Wt = 0.9 |conf| + 0.1, k = [lo <= y <= hi] (the thresholds
+ * are constants: the reference only compares against them), x = (scale, shift),
+ * N = [[s11, s12], [s12, s22]], v = N^-1 (g_scale, g_shift), u = a v0 + v1, r = y - (a x0 + x1):
+ *   grad_disp = k Wt u [disp > 0]
+ *   grad_conf = 0.9 sign(conf) k u r
+ *   grad_mde  = sign(mde) k Wt (v0 r - u x0)                  (sign(0) = 0)
+ * A sample whose record flags the rank-deficient or the empty branch gets all-zero gradients: the
+ * forward took its minimum-norm / zero branch there, and the reference's GPU lstsq assumes full rank,
+ * so there is nothing to match.  Every output pointer may be NULL (not computed; at least one is
+ * given); every element of a requested output is written. */
+int sa_weighted_lsq_backward(const float *mde, const float *disp, const float *conf, int B, int n_per_b,
+                             const float *scale, const float *shift, const double *rec,
+                             const float *g_scale, const float *g_shift, float *grad_mde, float *grad_disp,
+                             float *grad_conf, void *stream);
 
 /* a7 + a8 + a11 — scaled mono (stereoanywhere.py:194-197), its softLRC (199), the mirror
  * detector (utils.py:255-269) and the initial coordinates (stereoanywhere.py:261-262):

@@ -100,7 +100,11 @@ SIGNATURES = {
     "sa_clock_probe": (I, [I, I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     "sa_flow_head_reduce": (I, [P, I, I, I, I, P, P, P, L, P, L, P]),
     "sa_softlrc": (I, [P, P, P, P, I, I, I, L, F, P, P, P]),
+    "sa_softlrc_backward_ws_size": (L, [I, I, I]),
+    "sa_softlrc_backward": (I, [P, P, P, P, I, I, I, L, F, P, P, P, P, P, P, P, P]),
     "sa_weighted_lsq": (I, [P, P, P, I, I, F, F, P, P, P]),
+    "sa_weighted_lsq_stats": (I, [P, P, P, I, I, F, F, P, P, P, P]),
+    "sa_weighted_lsq_backward": (I, [P, P, P, I, I, P, P, P, P, P, P, P, P, P]),
     "sa_weighted_lsq_ws_size": (L, [I, I]),
     "sa_weighted_lsq_ws": (I, [P, P, P, I, I, F, F, P, P, P, P]),
     "sa_mono_scale_mirror": (I, [P, P, P, P, P, P, I, I, I, L, F, F, P, P, P, P, P]),

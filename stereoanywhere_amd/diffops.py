@@ -1,17 +1,27 @@
-"""Differentiable drop-ins for the reference's soft-argmin / entropy-confidence functions and its
-convex up-sampling (models/stereoanywhere/utils/utils.py:97-170).
+"""Differentiable drop-ins for the reference's soft-argmin / entropy-confidence functions, its
+convex up-sampling, its soft left-right consistency and its weighted least-squares scale / shift
+(models/stereoanywhere/utils/utils.py:97-198, 345-384).
 
 ``estimate_left_disparity``, ``estimate_right_disparity``, ``estimate_left_confidence``,
-``estimate_right_confidence`` and ``convex_upflow`` keep the reference's names and signatures;
-``softargmin_conf`` is the joint form (all four maps of a disparity and a confidence volume from one
-forward and one backward) and the one to prefer: four separate calls are four forwards, four
-backwards and two volume-sized additions by autograd.
+``estimate_right_confidence``, ``convex_upflow``, ``softlrc`` and ``weighted_lsq`` keep the
+reference's names and signatures; ``softargmin_conf`` is the joint form (all four maps of a disparity
+and a confidence volume from one forward and one backward) and the one to prefer: four separate calls
+are four forwards, four backwards and two volume-sized additions by autograd.  ``softlrc_conf`` is
+``fuzzy_and(conf, softlrc)`` of both maps in one launch, as the model's forward uses it.
 
 With grad mode on and an input that requires grad the functions run as the autograd functions below:
-the forward is the inference kernel (``ops.softargmin_conf`` / ``ops.convex_upsample``, so the same
-bits), the backward a deterministic HIP adjoint (csrc/diffops_backward.hip) that recomputes the
-softmaxes from the saved inputs; nothing but the inputs is saved.  Otherwise they make the plain
-``ops`` calls and return tensors without a ``grad_fn``.  Double backward is not built.
+the forward is the inference kernel (``ops.softargmin_conf`` / ``ops.convex_upsample`` /
+``ops.softlrc`` / the one-launch ``ops.weighted_lsq``, so the same bits), the backward a
+deterministic HIP adjoint (csrc/diffops_backward.hip, csrc/lsq_backward.hip) that recomputes the
+forward from the saved inputs; nothing but the inputs is saved, plus for ``weighted_lsq`` its two
+outputs and a record of six doubles per sample (the band thresholds, the normal-equation sums, the
+branch taken).  Otherwise they make the plain ``ops`` calls and return tensors without a ``grad_fn``.
+Double backward is not built.
+
+``weighted_lsq`` gives all-zero gradients for a sample whose kept mono values are all equal or whose
+band is empty: the forward takes its minimum-norm / zero branch there, and the reference's GPU
+``lstsq`` assumes full rank, so there is nothing to match.  The band thresholds are constants, as in
+the reference, which only compares against them.
 
 Floating inputs that are not fp32 (fp16 / bf16 activations under ``torch.autocast``) are cast with
 ``.float()``: a torch op, so the gradient arrives at the caller's tensor in its own dtype.  There is
@@ -177,3 +187,97 @@ def convex_upflow(flow, mask, n_downsample=2, use_scale_factor=True):
     if _wants_grad(flow, mask):
         return _ConvexUpFn.apply(flow, mask, factor, bool(use_scale_factor))
     return _upsample(flow, mask, factor, use_scale_factor)
+
+
+# --------------------------------------------------------------- softLRC and weighted_lsq
+class _SoftLrcFn(torch.autograd.Function):
+    """ops.softlrc with ops.softlrc_backward as its adjoint.  Saves the maps only; an output nobody
+    used arrives as a None gradient and is passed on as a null pointer."""
+
+    @staticmethod
+    def forward(ctx, d2, d3, conf2, conf3, lrc_th):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(d2, d3, conf2, conf3)
+        ctx.lrc_th = lrc_th
+        return ops.softlrc(d2, d3, conf2, conf3, lrc_th)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_s2, g_s3):
+        d2, d3, conf2, conf3 = ctx.saved_tensors
+        need = ctx.needs_input_grad[:4]
+        if (g_s2 is None and g_s3 is None) or not any(need):
+            return None, None, None, None, None
+        g_s2, g_s3 = (None if g is None else g.float().contiguous() for g in (g_s2, g_s3))
+        return (*ops.softlrc_backward(d2, d3, conf2, conf3, ctx.lrc_th, g_s2, g_s3, *need), None)
+
+
+def _lrc_map(t: Optional[torch.Tensor], name: str, like: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    _on_gpu(t, name)
+    if t.dim() != 4 or t.shape[1] != 1:
+        raise RuntimeError(f"{name} must be [B,1,H,W], got {tuple(t.shape)}")
+    if like is not None and t.shape != like.shape:
+        raise RuntimeError(f"{name} must have the shape of disp2 {tuple(like.shape)}, got {tuple(t.shape)}")
+    return t.float().contiguous()
+
+
+def _softlrc(disp2, disp3, conf2, conf3, lrc_th):
+    d2 = _lrc_map(disp2, "disp2")
+    d3, c2, c3 = (_lrc_map(t, n, d2) for t, n in ((disp3, "disp3"), (conf2, "conf2"), (conf3, "conf3")))
+    if _wants_grad(d2, d3, c2, c3):
+        return _SoftLrcFn.apply(d2, d3, c2, c3, float(lrc_th))
+    return ops.softlrc(d2, d3, c2, c3, float(lrc_th))
+
+
+def softlrc(disp2, disp3, lrc_th=1.0):
+    """The reference's softlrc: disparity maps [B,1,H,W] -> (softlrc_disp2, softlrc_disp3)."""
+    return _softlrc(disp2, disp3, None, None, lrc_th)
+
+
+def softlrc_conf(disp2, disp3, conf2, conf3, lrc_th=1.0):
+    """(fuzzy_and(conf2, softlrc_disp2), fuzzy_and(conf3, softlrc_disp3)) in one launch, forward and
+    backward: the pair the reference's forward feeds to weighted_lsq and the mirror detector."""
+    if conf2 is None or conf3 is None:
+        raise RuntimeError("softlrc_conf: conf2 and conf3 must be given (softlrc is the form without them)")
+    return _softlrc(disp2, disp3, conf2, conf3, lrc_th)
+
+
+class _WeightedLsqFn(torch.autograd.Function):
+    """ops.weighted_lsq_stats (the bits of ops.weighted_lsq) with ops.weighted_lsq_backward as its
+    adjoint.  Saves the three maps, the two outputs and the per-sample record."""
+
+    @staticmethod
+    def forward(ctx, mde, disp, conf, q_lo, q_hi):
+        ctx.set_materialize_grads(False)
+        scale, shift, rec = ops.weighted_lsq_stats(mde, disp, conf, q_lo, q_hi)
+        ctx.save_for_backward(mde, disp, conf, scale, shift, rec)
+        return scale, shift
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_scale, g_shift):
+        mde, disp, conf, scale, shift, rec = ctx.saved_tensors
+        need = ctx.needs_input_grad[:3]
+        if (g_scale is None and g_shift is None) or not any(need):
+            return None, None, None, None, None
+        g_scale, g_shift = (None if g is None else g.float().contiguous() for g in (g_scale, g_shift))
+        return (*ops.weighted_lsq_backward(mde, disp, conf, scale, shift, rec, g_scale, g_shift, *need), None, None)
+
+
+def weighted_lsq(mde, disp, conf, min_quantile=0.2, max_quantile=0.9):
+    """The reference's weighted_lsq: maps [B, ...] of one shape, flattened per sample -> (scale, shift),
+    [B,1,1,1] each in mde's dtype."""
+    for t, name in ((mde, "mde"), (disp, "disp"), (conf, "conf")):
+        _on_gpu(t, name)
+        if t.dim() < 2 or t.shape != mde.shape:
+            raise RuntimeError(f"weighted_lsq: {name} must be [B, ...] of mde's shape {tuple(mde.shape)}, "
+                               f"got {tuple(t.shape)}")
+    B = mde.shape[0]
+    m, d, c = (t.reshape(B, -1).float().contiguous() for t in (mde, disp, conf))
+    if _wants_grad(m, d, c):
+        scale, shift = _WeightedLsqFn.apply(m, d, c, float(min_quantile), float(max_quantile))
+    else:
+        scale, shift = ops.weighted_lsq(m, d, c, float(min_quantile), float(max_quantile))
+    return scale.reshape(B, 1, 1, 1).to(mde.dtype), shift.reshape(B, 1, 1, 1).to(mde.dtype)

@@ -572,6 +572,112 @@ def weighted_lsq(mde: torch.Tensor, disp: torch.Tensor, conf: torch.Tensor, q_lo
     return scale, shift
 
 
+def _lrc_maps(d2, d3, conf2, conf3, who: str):
+    """Shape checks of separate [B,1,H,W] softlrc maps -> (B, H, W)."""
+    _check(d2, "d2")
+    if d2.dim() != 4 or d2.shape[1] != 1:
+        raise RuntimeError(f"{who}: d2 must be [B,1,H,W], got {tuple(d2.shape)}")
+    for t, nm in ((d3, "d3"), (conf2, "conf2"), (conf3, "conf3")):
+        if t is None and nm != "d3":
+            continue
+        _check(t, nm)
+        if t.shape != d2.shape:
+            raise RuntimeError(f"{who}: {nm} must have d2's shape {tuple(d2.shape)}, got {tuple(t.shape)}")
+    B, _, H, W = d2.shape
+    return B, H, W
+
+
+def softlrc(d2: torch.Tensor, d3: torch.Tensor, conf2: Optional[torch.Tensor] = None,
+            conf3: Optional[torch.Tensor] = None, lrc_th: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """softlrc of separate, contiguous [B,1,H,W] disparity maps, each times its confidence (fuzzy_and)
+    when given -> (s2, s3) [B,1,H,W].  The kernel of softlrc_joint with map_bs = H*W."""
+    B, H, W = _lrc_maps(d2, d3, conf2, conf3, "softlrc")
+    s2, s3 = torch.empty_like(d2), torch.empty_like(d3)
+    N.call("sa_softlrc", d2.data_ptr(), d3.data_ptr(), _ptr(conf2), _ptr(conf3), B, H, W, H * W, lrc_th,
+           s2.data_ptr(), s3.data_ptr(), _stream(d2))
+    return s2, s3
+
+
+def softlrc_backward(d2: torch.Tensor, d3: torch.Tensor, conf2: Optional[torch.Tensor],
+                     conf3: Optional[torch.Tensor], lrc_th: float, g_s2: Optional[torch.Tensor],
+                     g_s3: Optional[torch.Tensor], need_d2: bool = True, need_d3: bool = True,
+                     need_conf2: bool = False, need_conf3: bool = False):
+    """Adjoint of softlrc: maps and upstream gradients contiguous [B,1,H,W]; g_s2 / g_s3 None: that
+    output was not used.  -> (grad_d2, grad_d3, grad_conf2, grad_conf3); an output that is not needed
+    is None and is not computed.  Deterministic."""
+    B, H, W = _lrc_maps(d2, d3, conf2, conf3, "softlrc_backward")
+    for t, nm in ((g_s2, "g_s2"), (g_s3, "g_s3")):
+        if t is not None:
+            _check(t, nm)
+            if t.shape != d2.shape:
+                raise RuntimeError(f"softlrc_backward: {nm} must have d2's shape {tuple(d2.shape)}, got {tuple(t.shape)}")
+    if (need_conf2 and conf2 is None) or (need_conf3 and conf3 is None):
+        raise RuntimeError("softlrc_backward: a confidence gradient is asked for without that confidence")
+    if not (need_d2 or need_d3 or need_conf2 or need_conf3) or (g_s2 is None and g_s3 is None):
+        raise RuntimeError("softlrc_backward: nothing to compute")
+    outs = [torch.empty_like(d2) if need else None for need in (need_d2, need_d3, need_conf2, need_conf3)]
+    ws = None
+    if (need_d2 and g_s3 is not None) or (need_d3 and g_s2 is not None):   # a gather follows
+        ws = torch.empty((N.lib().sa_softlrc_backward_ws_size(B, H, W) // 8,), device=d2.device, dtype=torch.float64)
+    N.call("sa_softlrc_backward", d2.data_ptr(), d3.data_ptr(), _ptr(conf2), _ptr(conf3), B, H, W, H * W, lrc_th,
+           _ptr(g_s2), _ptr(g_s3), *[_ptr(o) for o in outs], _ptr(ws), _stream(d2))
+    return tuple(outs)
+
+
+LSQ_REC = 6   # SA_LSQ_REC: doubles per sample of the weighted_lsq record
+
+
+def _lsq_maps(mde, disp, conf, who: str):
+    for t, nm in ((mde, "mde"), (disp, "disp"), (conf, "conf")):
+        _check(t, nm)
+        if t.shape != mde.shape:
+            raise RuntimeError(f"{who}: {nm} must have mde's shape {tuple(mde.shape)}, got {tuple(t.shape)}")
+    if mde.dim() < 2 or mde.numel() == 0:
+        raise RuntimeError(f"{who}: the maps must be [B, ...] and not empty, got {tuple(mde.shape)}")
+    B = mde.shape[0]
+    return B, mde.numel() // B
+
+
+def weighted_lsq_stats(mde: torch.Tensor, disp: torch.Tensor, conf: torch.Tensor, q_lo: float = 0.2,
+                       q_hi: float = 0.9):
+    """weighted_lsq (the one-launch form, the same bits) plus the per-sample record its backward needs
+    -> (scale [B], shift [B], rec [B, LSQ_REC] float64: s11, s12, s22, lo, hi, branch flag)."""
+    B, n = _lsq_maps(mde, disp, conf, "weighted_lsq_stats")
+    scale = torch.empty(B, device=mde.device, dtype=torch.float32)
+    shift = torch.empty(B, device=mde.device, dtype=torch.float32)
+    rec = torch.empty((B, LSQ_REC), device=mde.device, dtype=torch.float64)
+    N.call("sa_weighted_lsq_stats", mde.data_ptr(), disp.data_ptr(), conf.data_ptr(), B, n, q_lo, q_hi,
+           scale.data_ptr(), shift.data_ptr(), rec.data_ptr(), _stream(mde))
+    return scale, shift, rec
+
+
+def weighted_lsq_backward(mde: torch.Tensor, disp: torch.Tensor, conf: torch.Tensor, scale: torch.Tensor,
+                          shift: torch.Tensor, rec: torch.Tensor, g_scale: Optional[torch.Tensor],
+                          g_shift: Optional[torch.Tensor], need_mde: bool = True, need_disp: bool = True,
+                          need_conf: bool = True):
+    """Adjoint of weighted_lsq_stats: the forward's maps, its (scale, shift, rec) and the upstream
+    gradients g_scale / g_shift [B] (None: that output was not used) -> (grad_mde, grad_disp,
+    grad_conf) shaped like the maps; an output that is not needed is None and is not computed.  A
+    sample on the rank-deficient or the empty branch gets zeros.  Deterministic."""
+    B, n = _lsq_maps(mde, disp, conf, "weighted_lsq_backward")
+    for t, nm in ((scale, "scale"), (shift, "shift"), (g_scale, "g_scale"), (g_shift, "g_shift")):
+        if t is None and nm[0] == "g":
+            continue
+        _check(t, nm)
+        if t.numel() != B:
+            raise RuntimeError(f"weighted_lsq_backward: {nm} must hold B = {B} floats, got {tuple(t.shape)}")
+    if not isinstance(rec, torch.Tensor) or rec.device.type != "cuda" or rec.dtype != torch.float64 \
+            or tuple(rec.shape) != (B, LSQ_REC) or not rec.is_contiguous():
+        raise RuntimeError(f"weighted_lsq_backward: rec must be the contiguous float64 [{B}, {LSQ_REC}] GPU record of "
+                           "weighted_lsq_stats")
+    if not (need_mde or need_disp or need_conf) or (g_scale is None and g_shift is None):
+        raise RuntimeError("weighted_lsq_backward: nothing to compute")
+    outs = [torch.empty_like(mde) if need else None for need in (need_mde, need_disp, need_conf)]
+    N.call("sa_weighted_lsq_backward", mde.data_ptr(), disp.data_ptr(), conf.data_ptr(), B, n, scale.data_ptr(),
+           shift.data_ptr(), rec.data_ptr(), _ptr(g_scale), _ptr(g_shift), *[_ptr(o) for o in outs], _stream(mde))
+    return tuple(outs)
+
+
 def mono_scale_mirror(mde_lr: torch.Tensor, scale, shift, disp: torch.Tensor, conf: torch.Tensor, lrc_th: float,
                       conf_th: float):
     """From [B,2,H,W] mono / disparity / confidence buffers -> sm2, sm3, mirror, coords_x [B,1,H,W]."""
