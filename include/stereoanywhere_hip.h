@@ -31,14 +31,16 @@ extern "C" {
  * stride, so a host built against another layout would hand over misread fields.
  *   9: sa_corr_lookup_backward / sa_corr_pyramid_backward / sa_corr_volume_backward (additive);
  *      later, still 9: sa_softargmin_conf_backward(_ws_size) / sa_convex_upsample_backward (additive);
- *      sa_softlrc_backward(_ws_size) / sa_weighted_lsq_stats / sa_weighted_lsq_backward (additive)
+ *      sa_softlrc_backward(_ws_size) / sa_weighted_lsq_stats / sa_weighted_lsq_backward (additive);
+ *      sa_loss_terms_forward / sa_loss_terms_backward / their two sizes / SaLossMap (additive)
  *   8: block_shape 7 of sa_conv2d_k3_wino4_multi_gate / sa_conv2d_k3_wino4_launch (additive)
  *   7: sa_feature_gates / SaFeatureGateJob added (additive: no earlier entry point changed)
  *   6: round 6 (the implicit-GEMM entry points removed; sa_struct_size, sa_conv3d_mf_get_planes)
  *   5: SaWinoProblem gained the residual-epilogue fields (skip ... out_act); sa_conv2d_k3_wino4_launch
  *      took a guard flag; sa_conv2d_wino4_weights_cb removed */
 #define SA_ABI_VERSION 9
-enum { SA_STRUCT_WINO_PROBLEM = 0, SA_STRUCT_GATE_EPILOGUE = 1, SA_STRUCT_RESAMPLE_JOB = 2, SA_STRUCT_FEATURE_GATE_JOB = 3 };
+enum { SA_STRUCT_WINO_PROBLEM = 0, SA_STRUCT_GATE_EPILOGUE = 1, SA_STRUCT_RESAMPLE_JOB = 2, SA_STRUCT_FEATURE_GATE_JOB = 3,
+       SA_STRUCT_LOSS_MAP = 4 };
 int sa_abi_version(void);
 /* sizeof the struct `which` (SA_STRUCT_*) as the library was built, -1 for an unknown id */
 long sa_struct_size(int which);
@@ -787,6 +789,88 @@ int sa_norm_act(const float *x, long x_bs, int B, int C, long hw, const float *m
                 const float *t, int pstride, int act_in, const float *skip, long skip_bs,
                 const float *skip_m, const float *skip_s, const float *skip_t, int skip_pstride,
                 int act_skip, int act_out, float *out, long out_bs, void *stream);
+
+/* ----------------------------------------------------------------------------------
+ * The fused training loss (train.py:281-379): the L1, normals and confidence-BCE terms of K maps
+ * against one ground truth, forward and backward.  This comment is where the semantics are
+ * written down; csrc/losses.hip, stereoanywhere_amd/losses.py and tests/losses_ref.py follow it.
+ *
+ * Inputs: K >= 1 maps m_k [B,1,H,W] (fp32, dense), gt and valid [B,1,H,W], the scalar maxdisp;
+ * optionally target normals t [B,3,H,W] with the scalar gain; optionally per map a confidence c_k
+ * [B,1,H,W] with the scalar lrc_th.  Per map (SaLossMap): sign in {-1, +1}; the selection sel in
+ * {mask, mask and border}; the weights w_l1, w_n, w_bce (0: the term is not computed); flags.
+ *   x      = sign m_k
+ *   mask   = (valid > 0) and (gt < maxdisp)
+ *   border = all true (SA_LOSS_BORDER_NONE); col - gt >= 0 (SA_LOSS_BORDER_LEFT, train.py:319);
+ *            col + gt < W (SA_LOSS_BORDER_RIGHT, train.py:348)
+ * Counts are global over the batch, as pred[mask].mean() is.
+ *   L1_k   = mean over sel of |x - gt|
+ *   N_k    = mean over sel of (1 - n . t), following normalize (utils.py:56-71), estimate_normals
+ *            (utils.py:73-77) and correlation_score (utils.py:285-293): mn, mx the per-sample minimum and
+ *            maximum of x over the whole plane (masked pixels included; constants for the gradient, the
+ *            reference detaches them), z = (x - mn) / (mx - mn + 1e-4), g = gain z,
+ *            a = -(g[y, x+1] - g[y, x-1]), b = -(g[y+1, x] - g[y-1, x]) with clamped (replicate)
+ *            indices and no halving (oracle/ops_ref.py spatial_gradient_diff), n = (a, b, 1) / |(a, b, 1)|
+ *   BCE_k  = mean over {mask, c_k and tgt not NaN} of
+ *            -(tgt max(log c, -100) + (1 - tgt) max(log(1 - c), -100))          (train.py:338-344)
+ *            with e = |m_k - gt| (the map itself, not x),
+ *            tgt = clip(softplus(lrc_th - e) / log(1 + exp(lrc_th)), 0, 1), a constant, c = clip(c_k, 0, 1)
+ *   total  = sum over k of w_l1 L1_k + w_n N_k + w_bce BCE_k
+ * NaN rules, as train.py has them line by line: a map flagged SA_LOSS_SKIP_IF_NAN_MAP that holds a NaN
+ * anywhere contributes nothing and gets zero gradients (322, 351); a mean over an empty selection is
+ * NaN; a NaN N_k is always dropped (305, 330, 361; a map with a NaN has NaN mn / mx, so its N_k is
+ * NaN); a NaN L1_k is dropped with SA_LOSS_DROP_NAN_L1 (334, 365) and propagates without (299); a NaN
+ * BCE_k is dropped with SA_LOSS_DROP_NAN_BCE (316, 376) and propagates without (344).  A dropped term has
+ * a zero gradient; when the total is NaN the backward writes zeros, not NaNs.
+ *
+ * Backward: d total / d m_k and d total / d c_k times the upstream scalar, for the maps that ask.
+ * sign(0) = 0 for |.|; the clip has zero slope outside [0, 1] and at 0 and 1; max(log, -100) has zero
+ * slope below -100; tgt, mn and mx carry no gradient.  The stencil's adjoint is a gather: pixel q
+ * collects dL/da from (y, x-1) [-], itself if x = W-1 [-], itself if x = 0 [+], (y, x+1) [+], then dL/db
+ * from the rows likewise, into one accumulator in that order.
+ *
+ * Arithmetic: fp32 data, every element's arithmetic in fp64, each output rounded once.  Sums are fp64
+ * in a fixed order (lane tree, wave order, block order); no floating-point atomics: two runs give
+ * the same bits.  Neither call synchronises or copies between host and device: the SaLossMap array is
+ * host memory and travels in the kernel arguments, SA_LOSS_MAX_MAPS per launch; more maps take
+ * further launches.
+ *
+ * sa_loss_terms_forward: three launches per SA_LOSS_MAX_MAPS maps (per-(map, sample) mn / mx / NaN
+ * flag of the maps that need them; the partial sums, a block per 64 x 16 pixel tile that fetches gt,
+ * valid and t once and walks the maps; a one-block finalise).  It leaves
+ *   out [1 + 3 K] floats: the total, then L1_k, N_k, BCE_k per map (0 where a term is not computed
+ *       or its map was skipped; a dropped term shows its NaN),
+ *   rec, sa_loss_terms_rec_size(K, B) bytes, 8-byte aligned, doubles: [0] the total, [1] 1 if it is NaN,
+ *       [2] the count of mask, [3] of mask and border; then per map 8 doubles at 4 + 8 k: [0] 1 if
+ *       skipped, [1..3] the live terms' w / count (0: not computed, skipped or dropped), [4..6] the terms,
+ *       [7] the BCE count; then mn, mx per (map, sample) at 4 + 8 K + 2 (k B + b).
+ * ws: sa_loss_terms_ws_size(K, B, H, W) bytes, 8-byte aligned, for the forward only (-1: bad shape).
+ * target may be NULL when every w_n is 0, conf when w_bce is 0.  grad_map / grad_conf are not read.
+ *
+ * sa_loss_terms_backward: one launch per SA_LOSS_MAX_MAPS maps, a thread per pixel (64 x 4 tiles),
+ * recomputing from the inputs and rec; every element of each non-NULL grad_map / grad_conf is
+ * written.  g_total: the upstream scalar, one float on the device. */
+#define SA_LOSS_MAX_MAPS 32
+enum { SA_LOSS_SEL_MASK = 0, SA_LOSS_SEL_MASK_BORDER = 1 };
+enum { SA_LOSS_BORDER_NONE = 0, SA_LOSS_BORDER_LEFT = 1, SA_LOSS_BORDER_RIGHT = 2 };
+enum { SA_LOSS_SKIP_IF_NAN_MAP = 1, SA_LOSS_DROP_NAN_L1 = 2, SA_LOSS_DROP_NAN_BCE = 4 };
+typedef struct {
+  const float *map;    /* m_k */
+  const float *conf;   /* c_k, or NULL */
+  float *grad_map;     /* backward: d total / d m_k, or NULL */
+  float *grad_conf;    /* backward: d total / d c_k, or NULL */
+  double w_l1, w_n, w_bce;
+  int sign, sel, flags, reserved;
+} SaLossMap;
+long sa_loss_terms_ws_size(int K, int B, int H, int W);
+long sa_loss_terms_rec_size(int K, int B);
+int sa_loss_terms_forward(int K, const SaLossMap *maps, const float *gt, const float *valid,
+                          const float *target, int B, int H, int W, double maxdisp, int border_mode,
+                          double gain, double lrc_th, void *ws, double *rec, float *out, void *stream);
+int sa_loss_terms_backward(int K, const SaLossMap *maps, const float *gt, const float *valid,
+                           const float *target, int B, int H, int W, double maxdisp, int border_mode,
+                           double gain, double lrc_th, const double *rec, const float *g_total,
+                           void *stream);
 
 /* Live per-kernel timing for bench.py: when enabled, every launch of kernel `id`
  * is bracketed by hipEvents on the launch stream; sa_timing_read synchronises the

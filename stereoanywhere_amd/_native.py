@@ -20,6 +20,7 @@ P = ctypes.c_void_p
 I = ctypes.c_int
 L = ctypes.c_long
 F = ctypes.c_float
+D = ctypes.c_double
 
 # name -> (restype, argtypes); must match include/stereoanywhere_hip.h exactly
 class SaWinoProblem(ctypes.Structure):
@@ -47,6 +48,12 @@ class SaFeatureGateJob(ctypes.Structure):
     """include/stereoanywhere_hip.h: one DoubleFeatureAtt branch of sa_feature_gates."""
     _fields_ = [("in_", P), ("in_bs", L), ("B", I), ("H", I), ("W", I), ("w3", P), ("w1", P), ("b1", P),
                 ("C", I), ("out", P), ("out_bs", L)]
+
+
+class SaLossMap(ctypes.Structure):
+    """include/stereoanywhere_hip.h: one map of sa_loss_terms_forward / sa_loss_terms_backward."""
+    _fields_ = [("map", P), ("conf", P), ("grad_map", P), ("grad_conf", P), ("w_l1", D), ("w_n", D), ("w_bce", D),
+                ("sign", I), ("sel", I), ("flags", I), ("reserved", I)]
 
 
 SIGNATURES = {
@@ -107,6 +114,10 @@ SIGNATURES = {
     "sa_weighted_lsq_backward": (I, [P, P, P, I, I, P, P, P, P, P, P, P, P, P]),
     "sa_weighted_lsq_ws_size": (L, [I, I]),
     "sa_weighted_lsq_ws": (I, [P, P, P, I, I, F, F, P, P, P, P]),
+    "sa_loss_terms_ws_size": (L, [I, I, I, I]),
+    "sa_loss_terms_rec_size": (L, [I, I]),
+    "sa_loss_terms_forward": (I, [I, P, P, P, P, I, I, I, D, I, D, D, P, P, P, P]),
+    "sa_loss_terms_backward": (I, [I, P, P, P, P, I, I, I, D, I, D, D, P, P, P]),
     "sa_mono_scale_mirror": (I, [P, P, P, P, P, P, I, I, I, L, F, F, P, P, P, P, P]),
     "sa_gru_zr": (I, [P, L, P, P, L, P, P, L, P, L, I, I, I, P, P, P]),
     "sa_gru_out": (I, [P, L, P, P, L, P, L, P, I, I, I, P, L, P]),
@@ -230,8 +241,11 @@ def _check_abi(h) -> None:
     v = int(h.sa_abi_version())
     if v != ABI_VERSION:
         raise NativeError(f"{LIB_PATH} implements ABI version {v}, these bindings {ABI_VERSION}: rebuild it")
-    for which, st in ((0, SaWinoProblem), (1, SaGateEpilogue), (2, SaResampleJob), (3, SaFeatureGateJob)):
+    for which, st in ((0, SaWinoProblem), (1, SaGateEpilogue), (2, SaResampleJob), (3, SaFeatureGateJob),
+                      (4, SaLossMap)):
         got = int(h.sa_struct_size(which))
+        if got == -1 and os.environ.get("SA_HIP_LIB"):   # an older library of an A/B run has no such struct
+            continue
         if got != ctypes.sizeof(st):
             raise NativeError(f"{LIB_PATH}: {st.__name__} is {got} bytes in the library, "
                               f"{ctypes.sizeof(st)} in the bindings")

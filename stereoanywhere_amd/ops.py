@@ -11,7 +11,7 @@ import contextlib
 import ctypes
 import os
 import math
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -676,6 +676,112 @@ def weighted_lsq_backward(mde: torch.Tensor, disp: torch.Tensor, conf: torch.Ten
     N.call("sa_weighted_lsq_backward", mde.data_ptr(), disp.data_ptr(), conf.data_ptr(), B, n, scale.data_ptr(),
            shift.data_ptr(), rec.data_ptr(), _ptr(g_scale), _ptr(g_shift), *[_ptr(o) for o in outs], _stream(mde))
     return tuple(outs)
+
+
+# ------------------------------------------------------------------- the fused training loss
+LOSS_MAX_MAPS = 32                                   # SA_LOSS_MAX_MAPS: maps per launch
+LOSS_SEL_MASK, LOSS_SEL_MASK_BORDER = 0, 1           # SA_LOSS_SEL_*
+LOSS_BORDER = {"none": 0, "left": 1, "right": 2}     # SA_LOSS_BORDER_*
+LOSS_SKIP_IF_NAN_MAP, LOSS_DROP_NAN_L1, LOSS_DROP_NAN_BCE = 1, 2, 4   # SaLossMap.flags
+
+
+class LossMap(NamedTuple):
+    """One map of loss_terms and its constants (include/stereoanywhere_hip.h SaLossMap)."""
+    map: torch.Tensor
+    conf: Optional[torch.Tensor] = None
+    sign: int = 1
+    sel: int = LOSS_SEL_MASK
+    w_l1: float = 0.0
+    w_n: float = 0.0
+    w_bce: float = 0.0
+    flags: int = 0
+
+
+def _loss_maps(maps, gt, valid, target, border, who: str):
+    """Shape checks of the loss inputs -> (K, B, H, W, border mode)."""
+    if len(maps) < 1:
+        raise RuntimeError(f"{who}: at least one map is needed")
+    _check(gt, "gt")
+    if gt.dim() != 4 or gt.shape[1] != 1:
+        raise RuntimeError(f"{who}: gt must be [B,1,H,W], got {tuple(gt.shape)}")
+    B, _, H, W = gt.shape
+    _check(valid, "valid")
+    if valid.shape != gt.shape:
+        raise RuntimeError(f"{who}: valid must have gt's shape {tuple(gt.shape)}, got {tuple(valid.shape)}")
+    if target is not None:
+        _check(target, "target")
+        if tuple(target.shape) != (B, 3, H, W):
+            raise RuntimeError(f"{who}: target must be {(B, 3, H, W)}, got {tuple(target.shape)}")
+    for k, M in enumerate(maps):
+        for t, nm in ((M.map, f"map {k}"), (M.conf, f"conf {k}")):
+            if t is None and nm[0] == "c":
+                continue
+            _check(t, nm)
+            if t.shape != gt.shape:
+                raise RuntimeError(f"{who}: {nm} must have gt's shape {tuple(gt.shape)}, got {tuple(t.shape)}")
+        if M.w_n != 0 and target is None:
+            raise RuntimeError(f"{who}: map {k} has a normals weight but no target normals are given")
+        if M.w_bce != 0 and M.conf is None:
+            raise RuntimeError(f"{who}: map {k} has a BCE weight but no confidence")
+    if border not in LOSS_BORDER:
+        raise RuntimeError(f"{who}: border must be one of {sorted(LOSS_BORDER)}, got {border!r}")
+    return len(maps), B, H, W, LOSS_BORDER[border]
+
+
+def _loss_structs(maps, grad_maps=None, grad_confs=None):
+    arr = (N.SaLossMap * len(maps))()
+    for k, M in enumerate(maps):
+        arr[k] = N.SaLossMap(M.map.data_ptr(), _ptr(M.conf), _ptr(grad_maps[k]) if grad_maps else None,
+                             _ptr(grad_confs[k]) if grad_confs else None, float(M.w_l1), float(M.w_n),
+                             float(M.w_bce), int(M.sign), int(M.sel), int(M.flags), 0)
+    return arr
+
+
+def loss_terms(maps, gt: torch.Tensor, valid: torch.Tensor, maxdisp: float, target: Optional[torch.Tensor] = None,
+               gain: float = 1.0, border: str = "none", lrc_th: float = 1.0):
+    """The fused training loss of K maps (a sequence of LossMap; contiguous fp32 [B,1,H,W]) against gt /
+    valid [B,1,H,W], target normals [B,3,H,W] when a map has a normals weight -> (out [1 + 3 K] fp32:
+    the total, then L1_k, N_k, BCE_k; rec, the float64 record loss_terms_backward needs).  The
+    semantics are in include/stereoanywhere_hip.h.  No host synchronisation."""
+    K, B, H, W, mode = _loss_maps(maps, gt, valid, target, border, "loss_terms")
+    out = torch.empty(1 + 3 * K, device=gt.device, dtype=torch.float32)
+    rec = torch.empty(N.lib().sa_loss_terms_rec_size(K, B) // 8, device=gt.device, dtype=torch.float64)
+    ws = torch.empty(N.lib().sa_loss_terms_ws_size(K, B, H, W) // 8, device=gt.device, dtype=torch.float64)
+    N.call("sa_loss_terms_forward", K, _loss_structs(maps), gt.data_ptr(), valid.data_ptr(), _ptr(target), B, H, W,
+           float(maxdisp), mode, float(gain), float(lrc_th), ws.data_ptr(), rec.data_ptr(), out.data_ptr(),
+           _stream(gt))
+    return out, rec
+
+
+def loss_terms_backward(maps, gt: torch.Tensor, valid: torch.Tensor, maxdisp: float,
+                        target: Optional[torch.Tensor], gain: float, border: str, lrc_th: float,
+                        rec: torch.Tensor, g_total: torch.Tensor, need_map=None, need_conf=None):
+    """Adjoint of loss_terms: the forward's inputs and record, the upstream scalar g_total (one fp32
+    element on the GPU) -> (grad_maps, grad_confs), lists of K entries; need_map / need_conf: K flags
+    each (default: every map, no confidence); an entry that is not needed is None and is not computed.
+    Deterministic; no host synchronisation."""
+    K, B, H, W, mode = _loss_maps(maps, gt, valid, target, border, "loss_terms_backward")
+    need_map = [True] * K if need_map is None else list(need_map)
+    need_conf = [False] * K if need_conf is None else list(need_conf)
+    if len(need_map) != K or len(need_conf) != K:
+        raise RuntimeError(f"loss_terms_backward: need_map / need_conf must hold K = {K} flags")
+    if any(n and M.conf is None for n, M in zip(need_conf, maps)):
+        raise RuntimeError("loss_terms_backward: a confidence gradient is asked for without that confidence")
+    if not (any(need_map) or any(need_conf)):
+        raise RuntimeError("loss_terms_backward: nothing to compute")
+    if not isinstance(rec, torch.Tensor) or rec.device.type != "cuda" or rec.dtype != torch.float64 \
+            or rec.numel() != N.lib().sa_loss_terms_rec_size(K, B) // 8 or not rec.is_contiguous():
+        raise RuntimeError("loss_terms_backward: rec must be the contiguous float64 GPU record of loss_terms "
+                           f"for K = {K}, B = {B}")
+    _check(g_total, "g_total")
+    if g_total.numel() != 1:
+        raise RuntimeError(f"loss_terms_backward: g_total must hold one float, got {tuple(g_total.shape)}")
+    grad_maps = [torch.empty_like(M.map) if n else None for n, M in zip(need_map, maps)]
+    grad_confs = [torch.empty_like(M.conf) if n else None for n, M in zip(need_conf, maps)]
+    N.call("sa_loss_terms_backward", K, _loss_structs(maps, grad_maps, grad_confs), gt.data_ptr(), valid.data_ptr(),
+           _ptr(target), B, H, W, float(maxdisp), mode, float(gain), float(lrc_th), rec.data_ptr(),
+           g_total.data_ptr(), _stream(gt))
+    return grad_maps, grad_confs
 
 
 def mono_scale_mirror(mde_lr: torch.Tensor, scale, shift, disp: torch.Tensor, conf: torch.Tensor, lrc_th: float,
