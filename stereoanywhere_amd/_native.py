@@ -1,4 +1,9 @@
-"""ctypes binding of libsa_hip.so (the C ABI declared in include/stereoanywhere_hip.h).
+"""ctypes binding of libsa_hip.so, derived from the C ABI's one declaration.
+
+include/stereoanywhere_hip.h is the only place an entry point, a struct or a constant is declared:
+the .hip sources include it (the compiler checks each definition against it) and this module parses
+it at import into SIGNATURES, the Sa* ctypes structures and CONST.  A new entry point needs the
+header, its .hip definition and its ops wrapper, and nothing here.
 
 The library is built in-tree (``make`` or ``stereoanywhere_amd._native.build()``) so the
 .so travels with the repo snapshot to the GPU box.  There is no fallback: if the
@@ -7,7 +12,10 @@ library is missing every op raises, loudly.
 from __future__ import annotations
 
 import ctypes
+import keyword
 import os
+import re
+import shlex
 import subprocess
 from typing import Optional
 
@@ -22,165 +30,120 @@ L = ctypes.c_long
 F = ctypes.c_float
 D = ctypes.c_double
 
-# name -> (restype, argtypes); must match include/stereoanywhere_hip.h exactly
-class SaWinoProblem(ctypes.Structure):
-    """include/stereoanywhere_hip.h: one convolution of sa_conv2d_k3_wino_multi."""
-    _fields_ = [("in_", P), ("in_bs", L), ("N", I), ("Cin", I), ("H", I), ("W", I), ("U", P), ("Cout", I),
-                ("bias", P), ("relu", I), ("in_m", P), ("in_s", P), ("in_t", P), ("in_pstride", I),
-                ("in_act", I), ("out", P), ("out_bs", L), ("stats_partial", P), ("pitch", I),
-                ("skip", P), ("skip_bs", L), ("skip_s", P), ("skip_t", P), ("skip_act", I), ("out_act", I)]
+
+class NativeError(RuntimeError):
+    pass
 
 
-class SaGateEpilogue(ctypes.Structure):
-    """include/stereoanywhere_hip.h: ConvGRU gate epilogue of sa_conv2d_k3_wino4_multi_gate."""
-    _fields_ = [("mode", I), ("ctx", P), ("ctx_bs", L), ("h", P), ("h_bs", L), ("z", P), ("z_bs", L),
-                ("add", P), ("add_bs", L), ("out2", P), ("out2_bs", L), ("head_w", P), ("head_part", P),
-                ("head_part_bs", L)]
+_H = "include/stereoanywhere_hip.h"
+_SCALAR = {"int": I, "long": L, "float": F, "double": D}
+# [const] base-type [stars] [name]: one parameter, or the head of a struct field line
+_DECL = re.compile(r"(?:const\s+)?(\w+)\s*((?:\*\s*)*)(\w*)")
+_DECLARATOR = re.compile(r"((?:\*\s*)*)(\w+)")
 
 
-class SaResampleJob(ctypes.Structure):
-    """include/stereoanywhere_hip.h: one pool2x / interp job of sa_resample_multi."""
-    _fields_ = [("kind", I), ("in_", P), ("in_bs", L), ("in_pitch", I), ("B", I), ("C", I), ("H", I), ("W", I),
-                ("Ho", I), ("Wo", I), ("out", P), ("out_bs", L), ("out_pitch", I)]
+def _ctype(base: str, stars: str, decl: str):
+    """The type rule: any pointer is a void pointer, the four scalars map to their ctypes, and
+    anything else (unsigned, a struct by value, ...) is refused."""
+    if stars:
+        return P
+    if base not in _SCALAR:
+        raise NativeError(f"{_H}: cannot type `{decl}`")
+    return _SCALAR[base]
 
 
-class SaFeatureGateJob(ctypes.Structure):
-    """include/stereoanywhere_hip.h: one DoubleFeatureAtt branch of sa_feature_gates."""
-    _fields_ = [("in_", P), ("in_bs", L), ("B", I), ("H", I), ("W", I), ("w3", P), ("w1", P), ("b1", P),
-                ("C", I), ("out", P), ("out_bs", L)]
+def _struct_id(name: str) -> str:
+    """SaFeatureGateJob -> SA_STRUCT_FEATURE_GATE_JOB (the id sa_struct_size takes)."""
+    return "SA_STRUCT_" + re.sub(r"(?<!^)(?=[A-Z])", "_", name[2:]).upper()
 
 
-class SaLossMap(ctypes.Structure):
-    """include/stereoanywhere_hip.h: one map of sa_loss_terms_forward / sa_loss_terms_backward."""
-    _fields_ = [("map", P), ("conf", P), ("grad_map", P), ("grad_conf", P), ("w_l1", D), ("w_n", D), ("w_bce", D),
-                ("sign", I), ("sel", I), ("flags", I), ("reserved", I)]
+def parse_header(text: str):
+    """(signatures, structs, constants) of a header's text: every sa_* prototype as name ->
+    (restype, [argtypes]), every `typedef struct` as name -> ctypes.Structure class (fields in the
+    header's order), every integer #define SA_* and enumerator as name -> int.  A declaration the
+    type rule does not cover raises NativeError naming it: nothing is guessed or skipped."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants, structs, signatures = {}, {}, {}
+
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(SA_\w+)[ \t]*(.*)$", text, flags=re.M):
+        try:
+            constants[name] = int(value.strip(), 0)
+        except ValueError:
+            raise NativeError(f"{_H}: #define {name} {value.strip()} is not an integer") from None
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+
+    def enum(m):
+        nxt = 0
+        for item in filter(None, (s.strip() for s in m.group(1).split(","))):
+            name, _, value = (s.strip() for s in item.partition("="))
+            try:
+                nxt = int(value, 0) if value else nxt
+            except ValueError:
+                raise NativeError(f"{_H}: enumerator `{item}` is not an integer") from None
+            constants[name] = nxt
+            nxt += 1
+        return " "
+    text = re.sub(r"\benum\s*\w*\s*\{([^{}]*)\}\s*;", enum, text)
+
+    def struct(m):
+        fields = []
+        for line in filter(None, (s.strip() for s in m.group(1).split(";"))):
+            head = _DECL.match(line)
+            for d in line[head.end(1):].split(",") if head else [""]:
+                dm = _DECLARATOR.fullmatch(d.strip())
+                if dm is None:
+                    raise NativeError(f"{_H}: cannot type `{line}` of {m.group(2)}")
+                fname = dm.group(2) + ("_" if keyword.iskeyword(dm.group(2)) else "")
+                fields.append((fname, _ctype(head.group(1), dm.group(1), f"{line}` of `{m.group(2)}")))
+        structs[m.group(2)] = type(m.group(2), (ctypes.Structure,), {"_fields_": fields})
+        return " "
+    text = re.sub(r"\btypedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, text)
+
+    text, nopen = re.subn(r'\bextern\s+"C"\s*\{', " ", text)
+    if "{" in text or text.count("}") != nopen:
+        raise NativeError(f"{_H}: a braced block is neither an enum nor a typedef struct")
+    for stmt in filter(None, (" ".join(s.split()) for s in text.replace("}", " ").split(";"))):
+        m = re.fullmatch(r"(.*?)\b(sa_\w+) ?\(([^()]*)\)", stmt)
+        if m is None:
+            raise NativeError(f"{_H}: `{stmt}` is not an sa_* prototype")
+        ret = " ".join(m.group(1).replace("*", " * ").split())
+        if ret == "const char *":
+            restype = ctypes.c_char_p
+        elif ret == "void":
+            restype = None
+        elif ret in _SCALAR:
+            restype = _SCALAR[ret]
+        else:
+            raise NativeError(f"{_H}: cannot type the return of `{stmt}`")
+        argtypes = []
+        for arg in ([] if m.group(3).strip() in ("", "void") else m.group(3).split(",")):
+            am = _DECL.fullmatch(arg.strip())
+            if am is None:
+                raise NativeError(f"{_H}: cannot type `{arg.strip()}` of {m.group(2)}")
+            argtypes.append(_ctype(am.group(1), am.group(2), f"{arg.strip()}` of `{m.group(2)}"))
+        signatures[m.group(2)] = (restype, argtypes)
+
+    for name in structs:   # every struct has a size check at load time (_check_abi)
+        if _struct_id(name) not in constants:
+            raise NativeError(f"{_H}: struct {name} has no {_struct_id(name)} for sa_struct_size")
+    return signatures, structs, constants
 
 
-SIGNATURES = {
-    "sa_feature_gates_ws_size": (L, [I, P]),
-    "sa_feature_gates": (I, [I, P, P, P]),
-    "sa_abi_version": (I, []),
-    "sa_conv1x1_weights_size": (L, [I, I]),
-    "sa_conv1x1_weights": (I, [P, I, I, P, P]),
-    "sa_conv1x1": (I, [P, L, I, I, I, I, P, I, P, F, P, L, P]),
-    "sa_conv1x1_redo_blocks": (L, [I]),
-    "sa_mask_upsample": (I, [P, L, I, I, I, I, P, P, F, P, P, L, P]),
-    "sa_mask_upsample_redo_blocks": (L, [I]),
-    "sa_tile_gather_pad": (I, [P, I, I, I, P, I, I, I, I, I, I, I, P, P]),
-    "sa_tile_stitch": (I, [P, L, I, P, I, I, I, P, I, I, I, P, P, P]),
-    "sa_last_error": (ctypes.c_char_p, []),
-    "sa_pyramid_level_width": (I, [I, I]),
-    "sa_pyramid_level_offset": (I, [I, I]),
-    "sa_pyramid_row_stride": (L, [I, I]),
-    "sa_corr_volume_pyramid": (I, [P, P, I, I, I, I, I, F, P, P, F, I, P, L, P]),
-    "sa_corr_pyramid_from_volume": (I, [P, L, I, L, I, P, L, P]),
-    "sa_corr_pyramid_from_volume_strided": (I, [P, I, I, I, I, L, L, L, I, P, L, P]),
-    "sa_corr_lookup": (I, [P, P, I, L, I, I, P, L, I, I, I, P, L, P]),
-    "sa_corr_lookup_conv1x1": (I, [P, P, I, L, I, I, P, L, I, I, I, P, P, I, P, P]),
-    "sa_corr_lookup_backward": (I, [P, L, P, L, I, I, I, I, I, I, P, L, P]),
-    "sa_corr_pyramid_backward": (I, [P, L, I, L, I, P, L, P]),
-    "sa_corr_volume_backward": (I, [P, L, P, P, I, I, I, I, I, F, P, P, P]),
-    "sa_lookup_set_mfma": (None, [I]),
-    "sa_lookup_set_shear_dual": (None, [I]),
-    "sa_lookup_get_shear_dual": (I, []),
-    "sa_lookup_get_mfma": (I, []),
-    "sa_shear_slice_size": (L, [I, I, I]),
-    "sa_shear_row_pitch": (L, [I]),
-    "sa_corr_shear_supported": (I, [I, I, I, I, I]),
-    "sa_shear_level_offset": (L, [I, I, I, I]),
-    "sa_corr_pyramid_shear": (I, [P, L, I, I, I, I, I, P, P]),
-    "sa_corr_volume_pyramid_sheared": (I, [P, P, I, I, I, I, I, F, P, P, F, I, P, P]),
-    "sa_corr_pyramid_from_volume_strided_sheared": (I, [P, I, I, I, I, L, L, L, I, P, P]),
-    "sa_corr_lookup_conv1x1_sheared": (I, [P, P, I, I, I, P, L, I, I, I, P, P, I, P, P]),
-    "sa_mono_normals": (I, [P, I, I, I, F, P, P]),
-    "sa_mono_masked_volume": (I, [P, P, P, P, I, I, I, I, I, F, P, P]),
-    "sa_mono_bin_records": (I, [P, P, I, I, I, I, P, P]),
-    "sa_softargmin_conf": (I, [P, P, I, I, I, I, L, L, L, L, P, P, P, P, L, P]),
-    "sa_softargmin_set_one_pass": (None, [I]),
-    "sa_softargmin_get_one_pass": (I, []),
-    "sa_softargmin_conf_backward_ws_size": (L, [I, I, I, I]),
-    "sa_softargmin_conf_backward": (I, [P, P, I, I, I, I, L, L, L, L, P, P, P, P, P, P, P, P]),
-    "sa_convex_upsample_backward": (I, [P, P, L, P, I, I, I, I, F, P, P, P]),
-    "sa_split_redo_blocks": (L, [I]),
-    "sa_conv2d_k3_wino4_launch": (I, [I, P, P, I, I, P]),
-    "sa_flow_head_part_size": (L, [I, I, I, I]),
-    "sa_clock_probe": (I, [I, I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
-    "sa_flow_head_reduce": (I, [P, I, I, I, I, P, P, P, L, P, L, P]),
-    "sa_softlrc": (I, [P, P, P, P, I, I, I, L, F, P, P, P]),
-    "sa_softlrc_backward_ws_size": (L, [I, I, I]),
-    "sa_softlrc_backward": (I, [P, P, P, P, I, I, I, L, F, P, P, P, P, P, P, P, P]),
-    "sa_weighted_lsq": (I, [P, P, P, I, I, F, F, P, P, P]),
-    "sa_weighted_lsq_stats": (I, [P, P, P, I, I, F, F, P, P, P, P]),
-    "sa_weighted_lsq_backward": (I, [P, P, P, I, I, P, P, P, P, P, P, P, P, P]),
-    "sa_weighted_lsq_ws_size": (L, [I, I]),
-    "sa_weighted_lsq_ws": (I, [P, P, P, I, I, F, F, P, P, P, P]),
-    "sa_loss_terms_ws_size": (L, [I, I, I, I]),
-    "sa_loss_terms_rec_size": (L, [I, I]),
-    "sa_loss_terms_forward": (I, [I, P, P, P, P, I, I, I, D, I, D, D, P, P, P, P]),
-    "sa_loss_terms_backward": (I, [I, P, P, P, P, I, I, I, D, I, D, D, P, P, P]),
-    "sa_mono_scale_mirror": (I, [P, P, P, P, P, P, I, I, I, L, F, F, P, P, P, P, P]),
-    "sa_gru_zr": (I, [P, L, P, P, L, P, P, L, P, L, I, I, I, P, P, P]),
-    "sa_gru_out": (I, [P, L, P, P, L, P, L, P, I, I, I, P, L, P]),
-    "sa_gru_out_split": (I, [P, L, P, P, P, L, P, L, P, I, I, I, P, L, P]),
-    "sa_pool2x": (I, [P, L, I, I, I, I, P, L, P]),
-    "sa_interp_bilinear_ac": (I, [P, L, I, I, I, I, I, I, P, L, P]),
-    "sa_pool2x_p": (I, [P, L, I, I, I, I, I, P, L, I, P]),
-    "sa_interp_bilinear_ac_p": (I, [P, L, I, I, I, I, I, I, I, P, L, I, P]),
-    "sa_resample_multi": (I, [I, P, P]),
-    "sa_relu_copy": (I, [P, L, I, I, I, P, L, P]),
-    "sa_flow_update": (I, [P, P, L, I, I, I, P, L, P, L, P]),
-    "sa_convex_upsample": (I, [P, P, L, I, I, I, I, P, P]),
-    "sa_conv3d_stat_parts": (L, [I, I, I, I, I]),
-    "sa_conv3d": (I, [P, I, I, I, I, I, I, P, I, P, P, I, F, P, P, P, P, P]),
-    "sa_conv2d_k3_narrow": (I, [P, L, I, I, I, I, P, P, I, P, L, P]),
-    "sa_conv2d_wino_weights": (I, [P, I, I, P, P]),
-    "sa_conv2d_k3_wino": (I, [P, L, I, I, I, I, P, I, P, I, P, L, P]),
-    "sa_conv2d_k3_wino_stat_parts": (L, [I, I]),
-    "sa_conv2d_k3_wino_ex": (I, [P, L, I, I, I, I, P, I, P, I, P, P, P, I, I, P, L, P, P]),
-    "sa_conv2d_k3_wino_multi": (I, [I, P, P]),
-    "sa_conv2d_wino4_weights": (I, [P, I, I, P, P]),
-    "sa_conv2d_wino4_weights_split": (I, [P, I, I, P, P]),
-    "sa_conv2d_k3_wino4_stat_parts": (L, [I, I]),
-    "sa_conv2d_k3_wino4_multi": (I, [I, P, P]),
-    "sa_conv2d_k3_wino4_multi_gate": (I, [I, P, P, I, P]),
-    "sa_conv_direct_weights": (I, [P, I, I, I, I, I, P, P]),
-    "sa_conv_direct_weights_size": (L, [I, I, I, I, I]),
-    "sa_conv_direct_weights_split": (I, [P, L, P, P]),
-    "sa_conv_direct_stat_parts": (L, [I, I]),
-    "sa_conv_direct": (I, [P, L, I, I, I, I, I, I, P, P, I, P, L, P, L, P, P, P]),
-    "sa_conv_direct_split": (I, [P, L, I, I, I, I, I, I, P, P, I, P, L, P, L, P, P, P]),
-    "sa_conv_direct_close_supported": (I, [I, I, I]),
-    "sa_conv_direct_close": (I, [P, L, P, L, P, P, I, I, I, I, I, I, P, P, I, I, P, L, P, L, P, P, P]),
-    "sa_plane_stats": (I, [P, L, I, I, L, F, P, P, P]),
-    "sa_norm_act": (I, [P, L, I, I, L, P, P, P, I, I, P, L, P, P, P, I, I, I, P, L, P]),
-    "sa_conv3d_upcat_stat_parts": (L, [I, I, I]),
-    "sa_conv3d_wd_stat_parts": (L, [I, I, I, I]),
-    "sa_conv3d_pointwise": (I, [P, I, I, I, I, I, P, P, I, F, P, P, P, I, P, P]),
-    "sa_conv3d_pointwise_upcat": (I, [P, I, P, P, I, P, P, P, I, I, I, I, I, I, I, F, P, I, P, P, P]),
-    "sa_instnorm_finalize": (I, [P, I, L, L, F, P, P, P]),
-    "sa_conv3d_wd": (I, [P, I, I, I, I, I, P, I, P, P, I, F, P, P, P, P, P]),
-    "sa_conv3d_wd_set_variant": (None, [I]),
-    "sa_conv3d_wd_get_variant": (I, []),
-    "sa_conv3d_mf_weights_size": (L, [I, I]),
-    "sa_conv3d_mf_weights": (I, [P, I, I, P, P]),
-    "sa_conv3d_mf_stat_parts": (L, [I, I, I, I, I, I]),
-    "sa_conv3d_mf": (I, [P, I, I, I, I, I, P, I, P, P, F, P, P, P]),
-    "sa_conv3d_mf_set_planes": (None, [I]),
-    "sa_conv3d_mf_get_planes": (I, []),
-    "sa_struct_size": (L, [I]),
-    "sa_conv3d_s2mf_weights_size": (L, []),
-    "sa_conv3d_s2mf_weights": (I, [P, P, P]),
-    "sa_conv3d_s2mf_stat_parts": (L, [I, I, I]),
-    "sa_conv3d_s2mf": (I, [P, I, I, I, I, P, P, P, F, P, P, P, P, P]),
-    "sa_conv3d_onehot_stat_parts": (L, [I, I, I]),
-    "sa_conv3d_onehot": (I, [P, P, I, I, I, I, I, I, F, P, I, P, P, P]),
-    "sa_conv3d_pointwise_upcat_onehot": (I, [P, P, I, F, P, I, I, I, I, I, I, I, P, I, P, P, P]),
-    "sa_vol_apply": (I, [P, I, I, I, I, I, P, P, I, F, P, P, P, P]),
-    "sa_conv2d_small": (I, [P, L, I, I, I, I, P, P, I, I, I, P, L, P]),
-    "sa_timing_enable": (I, [I]),
-    "sa_timing_read": (I, [I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]),
-    "sa_kernel_name": (ctypes.c_char_p, [I]),
-}
+def _read_header() -> str:
+    try:
+        with open(HEADER) as f:
+            return f.read()
+    except OSError as e:
+        raise NativeError(f"{HEADER} is missing: the bindings are read from it ({e})") from None
+
+
+# SIGNATURES: name -> (restype, argtypes); STRUCTS: SaWinoProblem, SaGateEpilogue, SaResampleJob,
+# SaFeatureGateJob, SaLossMap (each also a name of this module); CONST: SA_* -> int
+SIGNATURES, STRUCTS, CONST = parse_header(_read_header())
+globals().update(STRUCTS)
+# the library must be built from the same header as these bindings (the struct arrays are read at
+# the library's stride)
+ABI_VERSION = CONST["SA_ABI_VERSION"]
 
 KERNEL_IDS = {
     "corr_volume_pyramid": 0, "corr_lookup": 1, "mono_masked_volume": 2, "softargmin_conf": 3,
@@ -192,10 +155,6 @@ KERNEL_IDS = {
 _lib: Optional[ctypes.CDLL] = None
 
 
-class NativeError(RuntimeError):
-    pass
-
-
 def build(verbose: bool = False) -> str:
     """Compile libsa_hip.so for gfx950 with hipcc (via the repo Makefile)."""
     cmd = ["make", "-C", ROOT, "-j8"]
@@ -205,6 +164,37 @@ def build(verbose: bool = False) -> str:
     if verbose:
         print(res.stdout)
     return LIB_PATH
+
+
+_USAGE_FIELDS = {"vgprs": r" VGPRs: (\d+)", "agprs": r" AGPRs: (\d+)", "scratch": r"ScratchSize \[bytes/lane\]: (\d+)",
+                 "lds": r"LDS Size \[bytes/block\]: (\d+)", "occupancy": r"Occupancy \[waves/SIMD\]: (\d+)"}
+
+
+def resource_usage(source_name: str, workdir, extra=()) -> dict:
+    """{mangled kernel name: {"vgprs", "agprs", "scratch", "lds", "occupancy"}} of one csrc/*.hip
+    source, from the resource-usage remarks of the product compile: the Makefile's own line for
+    that source (per-file flags included, plus `extra`), with the object written into workdir."""
+    stem = os.path.splitext(os.path.basename(source_name))[0]
+    target = f"build/{stem}.o"
+    dry = subprocess.run(["make", "-n", "-B", "-C", ROOT, target], capture_output=True, text=True)
+    lines = [shlex.split(ln) for ln in dry.stdout.splitlines()]
+    lines = [c for c in lines if "-c" in c and c[-2:] == ["-o", target]]
+    if dry.returncode != 0 or len(lines) != 1:
+        raise NativeError(f"make -n {target} gave no compile line:\n{dry.stdout}\n{dry.stderr}")
+    cmd = lines[0][:-1] + [os.path.join(str(workdir), f"{stem}.o"), "-Rpass-analysis=kernel-resource-usage", *extra]
+    res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
+    if res.returncode != 0:
+        raise NativeError(f"{' '.join(cmd)} failed:\n{res.stderr[-2000:]}")
+    out, cur = {}, None
+    for line in res.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            cur = out.setdefault(m.group(1), {})
+        for key, pat in _USAGE_FIELDS.items():
+            m = re.search(pat, line)
+            if m and cur is not None:
+                cur[key] = int(m.group(1))
+    return out
 
 
 def lib() -> ctypes.CDLL:
@@ -228,11 +218,6 @@ def lib() -> ctypes.CDLL:
     return _lib
 
 
-# include/stereoanywhere_hip.h SA_ABI_VERSION: the library must be built from the same header as
-# these bindings (the struct arrays are read at the library's stride)
-ABI_VERSION = 9
-
-
 def _check_abi(h) -> None:
     if not hasattr(h, "sa_abi_version"):
         if os.environ.get("SA_HIP_LIB"):   # an older library of an A/B run
@@ -241,13 +226,12 @@ def _check_abi(h) -> None:
     v = int(h.sa_abi_version())
     if v != ABI_VERSION:
         raise NativeError(f"{LIB_PATH} implements ABI version {v}, these bindings {ABI_VERSION}: rebuild it")
-    for which, st in ((0, SaWinoProblem), (1, SaGateEpilogue), (2, SaResampleJob), (3, SaFeatureGateJob),
-                      (4, SaLossMap)):
-        got = int(h.sa_struct_size(which))
+    for name, st in STRUCTS.items():
+        got = int(h.sa_struct_size(CONST[_struct_id(name)]))
         if got == -1 and os.environ.get("SA_HIP_LIB"):   # an older library of an A/B run has no such struct
             continue
         if got != ctypes.sizeof(st):
-            raise NativeError(f"{LIB_PATH}: {st.__name__} is {got} bytes in the library, "
+            raise NativeError(f"{LIB_PATH}: {name} is {got} bytes in the library, "
                               f"{ctypes.sizeof(st)} in the bindings")
 
 

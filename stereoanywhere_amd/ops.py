@@ -624,7 +624,7 @@ def softlrc_backward(d2: torch.Tensor, d3: torch.Tensor, conf2: Optional[torch.T
     return tuple(outs)
 
 
-LSQ_REC = 6   # SA_LSQ_REC: doubles per sample of the weighted_lsq record
+LSQ_REC = N.CONST["SA_LSQ_REC"]   # doubles per sample of the weighted_lsq record
 
 
 def _lsq_maps(mde, disp, conf, who: str):
@@ -679,10 +679,11 @@ def weighted_lsq_backward(mde: torch.Tensor, disp: torch.Tensor, conf: torch.Ten
 
 
 # ------------------------------------------------------------------- the fused training loss
-LOSS_MAX_MAPS = 32                                   # SA_LOSS_MAX_MAPS: maps per launch
-LOSS_SEL_MASK, LOSS_SEL_MASK_BORDER = 0, 1           # SA_LOSS_SEL_*
-LOSS_BORDER = {"none": 0, "left": 1, "right": 2}     # SA_LOSS_BORDER_*
-LOSS_SKIP_IF_NAN_MAP, LOSS_DROP_NAN_L1, LOSS_DROP_NAN_BCE = 1, 2, 4   # SaLossMap.flags
+LOSS_MAX_MAPS = N.CONST["SA_LOSS_MAX_MAPS"]          # maps per launch
+LOSS_SEL_MASK, LOSS_SEL_MASK_BORDER = N.CONST["SA_LOSS_SEL_MASK"], N.CONST["SA_LOSS_SEL_MASK_BORDER"]
+LOSS_BORDER = {k: N.CONST["SA_LOSS_BORDER_" + k.upper()] for k in ("none", "left", "right")}
+LOSS_SKIP_IF_NAN_MAP, LOSS_DROP_NAN_L1, LOSS_DROP_NAN_BCE = (   # SaLossMap.flags
+    N.CONST["SA_LOSS_SKIP_IF_NAN_MAP"], N.CONST["SA_LOSS_DROP_NAN_L1"], N.CONST["SA_LOSS_DROP_NAN_BCE"])
 
 
 class LossMap(NamedTuple):
@@ -889,7 +890,7 @@ def resample_multi(*jobs) -> None:
             B, _, H, W = x.shape
             if x.shape[1] != 1 or tuple(out.shape) != (B, 2, H, W):
                 raise RuntimeError(f"resample_multi: flow job coords {tuple(x.shape)} / planes {tuple(out.shape)}")
-            j.kind, j.in_, j.in_bs, j.in_pitch = 2, x.data_ptr(), x.stride(0), W
+            j.kind, j.in_, j.in_bs, j.in_pitch = N.CONST["SA_RESAMPLE_FLOW_X"], x.data_ptr(), x.stride(0), W
             j.B, j.C, j.H, j.W, j.Ho, j.Wo = B, 1, H, W, H, W
             j.out, j.out_bs, j.out_pitch = out.data_ptr(), _plane_bs(out, "flow_b"), W
             nbytes += 12.0 * B * H * W
@@ -906,7 +907,7 @@ def resample_multi(*jobs) -> None:
                                    f"{(B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1)}")
         if x.device != out.device:
             raise RuntimeError("resample_multi: x and out on different devices")
-        j.kind = 0 if kind == "pool" else 1
+        j.kind = N.CONST["SA_RESAMPLE_POOL2X" if kind == "pool" else "SA_RESAMPLE_BILINEAR_AC"]
         j.in_, j.in_bs, j.in_pitch = x.data_ptr(), _pitched_bs(x, "x"), Px
         j.B, j.C, j.H, j.W, j.Ho, j.Wo = B, C, H, W, Ho, Wo
         j.out, j.out_bs, j.out_pitch = out.data_ptr(), _pitched_bs(out, "out"), Po
@@ -931,8 +932,8 @@ def feature_gates(jobs) -> list:
     """The DoubleFeatureAtt branch outputs sigmoid(conv1x1(leaky(IN(conv3x3(feat))))) for up to 8
     jobs (feat [B, 1, H, W], (w3, w1, b1) from feature_gate_weights) in two launches
     (sa_feature_gates); returns a [B, C, H, W] tensor per job."""
-    if not 1 <= len(jobs) <= 8:
-        raise RuntimeError("feature_gates: 1..8 jobs")
+    if not 1 <= len(jobs) <= N.CONST["SA_GATE_MAX_JOBS"]:
+        raise RuntimeError(f"feature_gates: 1..{N.CONST['SA_GATE_MAX_JOBS']} jobs")
     arr = (N.SaFeatureGateJob * len(jobs))()
     outs = []
     nbytes = 0.0

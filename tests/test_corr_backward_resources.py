@@ -2,13 +2,11 @@
 from the compile's resource-usage remarks only: every kernel of corr_backward.hip runs without
 scratch.  The printed VGPR / AGPR / LDS figures are the ones in DESIGN.md's resource table."""
 import os
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "stereoanywhere_amd", "csrc")
+from stereoanywhere_amd._native import resource_usage
+
 HIPCC = "/opt/rocm/bin/hipcc"
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
@@ -17,28 +15,8 @@ KERNELS = ["lookup_backward_kernelILb1E", "lookup_backward_kernelILb0E", "pyrami
            "pyramid_backward_kernelILb0E", "volume_backward_kernelILb1E", "volume_backward_kernelILb0E"]
 
 
-def _usage(name, tmp_path):
-    """{kernel: {field: value}} from the compile's resource-usage remarks."""
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-           "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, name), "-o", str(tmp_path / "k.o")]
-    r = subprocess.run(cmd, cwd=tmp_path, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    fields = {"vgprs": r" VGPRs: (\d+)", "agprs": r" AGPRs: (\d+)", "scratch": r"ScratchSize \[bytes/lane\]: (\d+)",
-              "occupancy": r"Occupancy \[waves/SIMD\]: (\d+)", "lds": r"LDS Size \[bytes/block\]: (\d+)"}
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-        for key, pat in fields.items():
-            m = re.search(pat, line)
-            if m and cur is not None:
-                cur[key] = int(m.group(1))
-    return out
-
-
 def test_backward_kernels_do_not_spill(tmp_path):
-    usage = _usage("corr_backward.hip", tmp_path)
+    usage = resource_usage("corr_backward.hip", tmp_path)
     assert len(usage) == len(KERNELS), sorted(usage)
     for k in KERNELS:
         (name, u), = [(n, v) for n, v in usage.items() if k in n]

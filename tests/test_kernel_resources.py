@@ -2,45 +2,25 @@
 in the conv kernels whose second, rarely taken passes (the split kernels' range guards) share a
 body with the hot one, or whose register budget is near the limit (conv3d_s2mf: ~239 VGPRs)."""
 import os
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "stereoanywhere_amd", "csrc")
+from stereoanywhere_amd._native import resource_usage
+
 HIPCC = "/opt/rocm/bin/hipcc"
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 
 
-def _compile(name, tmp_path, extra=()):
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--save-temps",
-           "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, name), "-o",
-           str(tmp_path / "k.o"), *extra]
-    r = subprocess.run(cmd, cwd=tmp_path, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and cur:
-            usage[cur] = int(m.group(1))
-    stem = name.rsplit(".", 1)[0]
-    listing = tmp_path / f"{stem}-hip-amdgcn-amd-amdhsa-gfx950.s"
-    return usage, listing
-
-
-@pytest.mark.parametrize("name,kernel,extra", [
-    ("conv2d_wino4.hip", "wino_f4k3_kernel", ("-fno-slp-vectorize", "-mllvm", "-amdgpu-set-wave-priority")),
-    ("conv3d_mfma.hip", "conv3d_mf_kernel", ()),
-    ("conv3d_s2mf.hip", "conv3d_s2mf_kernel", ()),
+@pytest.mark.parametrize("name,kernel", [
+    ("conv2d_wino4.hip", "wino_f4k3_kernel"),
+    ("conv3d_mfma.hip", "conv3d_mf_kernel"),
+    ("conv3d_s2mf.hip", "conv3d_s2mf_kernel"),
 ])
-def test_conv_kernels_do_not_spill(tmp_path, name, kernel, extra):
-    usage, _ = _compile(name, tmp_path, extra)
-    hot = {k: v for k, v in usage.items() if kernel in k}
+def test_conv_kernels_do_not_spill(tmp_path, name, kernel):
+    usage = resource_usage(name, tmp_path)
+    hot = {k: u["scratch"] for k, u in usage.items() if kernel in k}
+    print({k: usage[k] for k in hot})
     assert hot, sorted(usage)
     # the one measured exception: the split F(4x4) kernel with the affine input on the paired loop
     # spills a few loop-invariant values and is faster than without (A/B in

@@ -4,13 +4,11 @@ The printed VGPR / LDS / occupancy figures are the ones in DESIGN.md section 4f.
 differentiable weighted_lsq (lsq_stats.hip) is the second instance of the inference kernel: it must
 use what the first one (lsq.hip) uses, no more."""
 import os
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "stereoanywhere_amd", "csrc")
+from stereoanywhere_amd._native import resource_usage
+
 HIPCC = "/opt/rocm/bin/hipcc"
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
@@ -18,32 +16,12 @@ pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not ins
 KERNELS = ["lrcb_px_kernel", "lrcb_gather_kernel", "lsqb_kernel"]
 
 
-def _usage(name, tmp_path):
-    """{kernel: {field: value}} from the compile's resource-usage remarks."""
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-           "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, name), "-o", str(tmp_path / "k.o")]
-    r = subprocess.run(cmd, cwd=tmp_path, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    fields = {"vgprs": r" VGPRs: (\d+)", "agprs": r" AGPRs: (\d+)", "scratch": r"ScratchSize \[bytes/lane\]: (\d+)",
-              "occupancy": r"Occupancy \[waves/SIMD\]: (\d+)", "lds": r"LDS Size \[bytes/block\]: (\d+)"}
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-        for key, pat in fields.items():
-            m = re.search(pat, line)
-            if m and cur is not None:
-                cur[key] = int(m.group(1))
-    return out
-
-
 def _show(k, u):
     print(f"{k}: VGPRs {u['vgprs']} AGPRs {u['agprs']} scratch {u['scratch']} LDS {u['lds']} occupancy {u['occupancy']}")
 
 
 def test_backward_kernels_do_not_spill(tmp_path):
-    usage = _usage("lsq_backward.hip", tmp_path)
+    usage = resource_usage("lsq_backward.hip", tmp_path)
     assert len(usage) == len(KERNELS), sorted(usage)
     for k in KERNELS:
         (name, u), = [(n, v) for n, v in usage.items() if k in n]
@@ -53,8 +31,8 @@ def test_backward_kernels_do_not_spill(tmp_path):
 
 
 def test_stats_instance_uses_what_the_inference_instance_uses(tmp_path):
-    (stats, s), = _usage("lsq_stats.hip", tmp_path).items()
-    (infer, i), = [(n, v) for n, v in _usage("lsq.hip", tmp_path).items() if "lsq1_kernel" in n]
+    (stats, s), = resource_usage("lsq_stats.hip", tmp_path).items()
+    (infer, i), = [(n, v) for n, v in resource_usage("lsq.hip", tmp_path).items() if "lsq1_kernel" in n]
     assert "lsq1_kernelILb1E" in stats and "lsq1_kernelILb0E" in infer
     _show("lsq1_kernel<true>", s)
     _show("lsq1_kernel<false>", i)
