@@ -66,13 +66,13 @@ __device__ __forceinline__ void hist_add(unsigned *h, unsigned bin, bool count) 
 //   A. a histogram of the top 15 bits of every key (relu'd values: sign 0, so 16384 bins of
 //      relative width 2^-6) in LDS; a wave per rank finds the rank's bin and the count below it
 //      (per-thread sums of 8 bins, then the bins of the one segment);
-//   B. the keys of the (at most 4, usually 2) selected bins and their indices are copied into an LDS
+//   B. the keys of the (at most 4, usually 2) selected bins are copied into an LDS
 //      pool at offsets known from the histogram (the pool holds 16384 keys: 25 % of a model sample);
 //      the same pass accumulates the normal equations of every key in a bin strictly between the
 //      lower and the upper quantile's bins (inside the band whatever the exact quantiles);
 //   C. a 9-bit and an 8-bit radix pass over each rank's bin (its pool slice) give the exact key;
-//      then the pooled keys inside the band add their terms (their mono / confidence values
-//      gathered by index).
+//      then one more pass over the keys, in index order, adds the terms of the selected bins' keys
+//      that are inside the band (the order of pool[] depends on wave timing; the sums must not).
 // A sample whose selected bins hold more keys than the pool (e.g. a quarter of the pixels at
 // one value) takes the four full 8-bit radix passes instead (lsq_select_radix below, the round-5
 // single-block algorithm) and a separate pass for the normal equations, in the same launch.
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(LSQ_THREADS) void lsq1_kernel(const float *__restri
                                                            float q_hi, float *__restrict__ scale,
                                                            float *__restrict__ shift, Rec... rec) {
   static_assert(sizeof...(Rec) == (STATS ? 1 : 0), "STATS takes the record pointer");
-  __shared__ unsigned hist[L1_BINS];           // pass A; then the pooled keys' indices
+  __shared__ unsigned hist[L1_BINS];           // pass A (the fallback: its digit histograms)
   __shared__ unsigned pool[L1_POOL];           // the selected bins' keys
   __shared__ unsigned seg[L1_BINS / L1_SEG];   // 8-bin sums; then [4][512] digit histograms
   static_assert(L1_BINS / L1_SEG >= 4 * 512 && L1_BINS >= L1_POOL, "LDS reuse");
@@ -304,11 +304,12 @@ __global__ __launch_bounds__(LSQ_THREADS) void lsq1_kernel(const float *__restri
     z12 += (double)a1 * w;
     z22 += (double)w * w;
   };
+  unsigned long long sel_mask = 0ull;   // bit i: key i * LSQ_THREADS + t is in a selected (pooled) bin, i < 64
   if (!fall) {
-    // B: copy the selected bins' keys (and indices) into their pool slices (wave-aggregated
-    // appends); the normal equations of the keys strictly between the quantiles' bins
+    // B: copy the selected bins' keys into their pool slices (wave-aggregated appends) and mark them
+    // in sel_mask; the normal equations of the keys strictly between the quantiles' bins
     const unsigned in_lo = lb[1], in_hi = lb[2];   // (b0 <= b1 <= b2 <= b3)
-    auto append = [&](unsigned k, int j, bool valid) __attribute__((always_inline)) {
+    auto append = [&](unsigned k, bool valid) __attribute__((always_inline)) {
       const unsigned bin = bin_of(k);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -323,7 +324,6 @@ __global__ __launch_bounds__(LSQ_THREADS) void lsq1_kernel(const float *__restri
         if (hit) {
           const unsigned at = s_off[r] + base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
           pool[at] = k;
-          hist[at] = (unsigned)j;
         }
       }
     };
@@ -341,7 +341,10 @@ __global__ __launch_bounds__(LSQ_THREADS) void lsq1_kernel(const float *__restri
       for (int c = 0; c < 8; ++c) {
         const int j = base + c * LSQ_THREADS + t;
         const unsigned bin = bin_of(kv[c]);
-        append(kv[c], j, j < n);
+        append(kv[c], j < n);
+        const int slot = base / LSQ_THREADS + c;
+        if (slot < 64 && j < n && bin != 0u && (bin == lb[0] || bin == lb[1] || bin == lb[2] || bin == lb[3]))
+          sel_mask |= 1ull << slot;
         if (j < n && bin > in_lo && bin < in_hi) add_terms(__uint_as_float(kv[c]), mv[c], cv[c]);
         if (zero_lo && j < n && bin == 0u) add_zero(mv[c], cv[c]);
       }
@@ -406,13 +409,28 @@ __global__ __launch_bounds__(LSQ_THREADS) void lsq1_kernel(const float *__restri
     s12 += z12;
     s22 += z22;
   }
-  if (!fall) {   // the pooled keys inside the band
-    const unsigned total = s_total;
-    for (unsigned e = t; e < total; e += LSQ_THREADS) {
-      const float d = __uint_as_float(pool[e]);
-      if (qlo <= d && d <= qhi) {
-        const unsigned j = hist[e];
-        add_terms(d, md[j], cd[j]);
+  if (!fall) {
+    // The boundary bins' keys inside the band, in index order: thread t takes j = t, t + 1024, ... as
+    // in pass B, so which thread adds a term, and after which others, depends on the key's index and
+    // value alone.  (Walking pool[] instead made both depend on where the waves' LDS appends of pass
+    // B had put the key, that is on wave timing.)  Pass B marked which of the thread's first 64 keys
+    // fell into a selected bin (sel_mask: the model's sample has 63.75 keys per thread), so only those
+    // are loaded again; keys past that are streamed and tested.  Nothing to add when no key was pooled.
+    if (s_total != 0u) {
+      for (unsigned long long mk = sel_mask; mk; mk &= mk - 1ull) {   // this thread's marked keys, ascending
+        const int j = (__ffsll((long long)mk) - 1) * LSQ_THREADS + t;
+        const float d = __uint_as_float(key_of(dd[j]));
+        if (qlo <= d && d <= qhi) add_terms(d, md[j], cd[j]);
+      }
+      if (n > 64 * LSQ_THREADS) {   // (past 64 keys per thread nothing was marked: test every key)
+        const int off = 64 * LSQ_THREADS;
+        lsq_stream_keys(dd + off, n - off, [&](unsigned k, int j, bool valid) {
+          const unsigned bin = bin_of(k);
+          const float d = __uint_as_float(k);
+          if (valid && bin != 0u && (bin == lb[0] || bin == lb[1] || bin == lb[2] || bin == lb[3]) && qlo <= d &&
+              d <= qhi)
+            add_terms(d, md[off + j], cd[off + j]);
+        });
       }
     }
   } else {   // (the fallback: every key against the band)

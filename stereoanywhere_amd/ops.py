@@ -1719,6 +1719,7 @@ def tile_stitch(disp: torch.Tensor, tiles: List[Tuple[int, int, int]], wgt: torc
                 finalize: bool, num: torch.Tensor, den: torch.Tensor) -> None:
     """The stitching loop of TileWrapper.forward in one launch (sa_tile_stitch): disp [n, 1, th, tw]
     (a view with any row pitch), tiles = (row, column, slot in disp) in the reference's order."""
+    _check(disp, "disp", contiguous=False)
     n, _, th, tw = disp.shape
     if disp.stride(3) != 1:
         raise RuntimeError("tile_stitch: disp rows must be contiguous")

@@ -281,8 +281,10 @@ class TileWrapper(torch.nn.Module):
                 disp = canonicalize(self.model(gp(left), gp(right), gp(mono_left), gp(mono_right), *args, **kw))
             hd, wd = disp.shape[-2:]
             outs = disp[..., _pad[2]:hd - _pad[3], _pad[0]:wd - _pad[1]]
-            if guide is None and outs.device == device and outs.shape[-2:] == (th, tw):
-                # the stitching loop below in one launch (sa_tile_stitch), same order, same bits
+            if guide is None and outs.device == device and outs.dtype == torch.float32 \
+                    and outs.shape[-2:] == (th, tw):
+                # the stitching loop below in one launch (sa_tile_stitch), same order, same bits (float32
+                # tiles only: the kernel reads floats; any other model output takes the torch loop)
                 slot = {s: i for i, s in enumerate(mine)}
                 wgt = blend_weight(th, tw, device).contiguous()
                 listed = [(s.y_start, s.x_start, slot[s]) for s in tiles if s in slot]

@@ -167,8 +167,12 @@ def test_batch_independence(model):
 
 
 def test_rerun_stability(model):
-    """The HIP kernels are deterministic (no float atomics); MIOpen may pick algorithms
-    whose sums differ in the last bit between runs, so reruns agree to fp32 noise."""
+    """The whole model twice: reruns agree to fp32 noise.  The HIP kernels themselves are held to equal
+    bits, op by op, by tests/test_gpu_invariance.py (reruns, replicas in one batch, dirty memory, two
+    streams).  This bound is loose for what is left on MIOpen, whose algorithm choice may change the
+    last bit between runs: today only fall-backs, namely a conv the fused kernels do not take
+    (encoders._conv: a 3x3 layer without Winograd filters; fnet's output 1x1 and the mask head's 1x1
+    where sa_conv1x1 does not apply: |w| >= 16, Cin % 32 != 0 or H W % 4 != 0)."""
     pb = synth.synthetic_batch(1, 128, 256, 48.0, seed0=9)
     a = run(model, pb, 5)
     b = run(model, pb, 5)

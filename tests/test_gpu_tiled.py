@@ -13,12 +13,14 @@ import pytest
 import torch
 
 from fixtures_util import epe, load_fixture
+from stereoanywhere_amd import ops as ops_mod
 from stereoanywhere_amd import synth, tiler
 from stereoanywhere_amd.model import StereoAnywhere
 from stereoanywhere_amd.offload import CPUOffloadWrapper
 
 pytestmark = pytest.mark.gpu
 PUBLISHED = dict(use_truncate_vol=True, use_aggregate_mono_vol=True)
+real_stitch = ops_mod.tile_stitch
 
 
 @pytest.fixture(scope="module")
@@ -132,3 +134,48 @@ def test_tile_gather_and_stitch_equal_torch_path(monkeypatch, H, W, th, tw, ov):
         seen[hip] = m.calls
     assert seen[True] == seen[False]
     assert torch.equal(out[True], out[False]), float((out[True] - out[False]).abs().max())
+
+
+class _DtypeMock(_GpuMock):
+    """_GpuMock whose output is cast to another dtype (an autocast / double-precision wrapped model)."""
+
+    def __init__(self, dtype):
+        super().__init__()
+        self.dtype = dtype
+
+    def forward(self, *a, **kw):
+        d, aux = super().forward(*a, **kw)
+        return d.to(self.dtype), aux
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.float64])
+def test_tile_stitch_non_fp32_model_output_takes_torch_loop(monkeypatch, dtype):
+    """A wrapped model that returns fp16 or fp64 tiles: sa_tile_stitch reads float32 only, so the
+    batched GPU path must hand such tiles to the torch loop and give its bits (the smallest two-tile
+    geometry: 64x160 in 64x96 tiles, overlap 32, two distinct rectangles)."""
+    H, W, th, tw, ov = 64, 160, 64, 96, 32
+    g = torch.Generator(device="cpu").manual_seed(7)
+    imgs = [torch.rand(1, c, H, W, generator=g).cuda() for c in (3, 3, 1, 1)]
+    stitched = []
+    monkeypatch.setattr(ops_mod, "tile_stitch", lambda *a, **k: stitched.append(a[0].dtype) or real_stitch(*a, **k))
+    out = {}
+    for hip in (True, False):
+        if not hip:
+            monkeypatch.setattr(tiler, "_hip_tiles", lambda *ts: False)
+        wrap = tiler.TileWrapper(_DtypeMock(dtype), tile_width=tw, tile_height=th, overlap=ov, batch_tiles=True)
+        out[hip] = wrap(*imgs, iters=1, test_mode=True)
+        assert wrap.last_tile_counts[1] == 2   # two rectangles (the enumeration lists them more than once)
+    assert stitched == [], "the one-launch stitch was handed non-float32 tiles"
+    assert out[True].dtype == out[False].dtype and out[True].shape == (1, 1, H, W)
+    assert torch.isfinite(out[False]).all()
+    assert torch.equal(out[True], out[False]), float((out[True] - out[False]).abs().max())
+
+
+def test_tile_stitch_refuses_fp16_disp():
+    th, tw, H, W = 8, 16, 8, 24
+    disp = torch.zeros(2, 1, th, tw, device="cuda", dtype=torch.float16)
+    wgt = torch.ones(th, tw, device="cuda")
+    num, den = torch.zeros(H, W, device="cuda"), torch.zeros(H, W, device="cuda")
+    with pytest.raises(RuntimeError, match="disp must be float32"):
+        ops_mod.tile_stitch(disp, [(0, 0, 0), (0, 8, 1)], wgt, H, W, True, num, den)
+    assert not num.any() and not den.any()
