@@ -872,6 +872,48 @@ int sa_loss_terms_backward(int K, const SaLossMap *maps, const float *gt, const 
                            double gain, double lrc_th, const double *rec, const float *g_total,
                            void *stream);
 
+/* The volume stage of the fine-tuning forward (volume_stage.hip): the volume-corruption augmentations
+ * (stereoanywhere.py:214-251) and the truncation multiply (201-205, 253-254) on an existing volume, one
+ * launch per touched volume and no host read.  Volumes are [B,1,H,W1,W2] contiguous fp32, element
+ * (b,h,j,k) with j on the left-pixel axis and k on the right-pixel axis; maps are [B,H,W1] fp32.
+ * Additive: no ABI version change; the launches are timed under SA_K_MISC.
+ *
+ * sa_volume_peak: peak[0] (device) = the maximum of volume[0 .. count), batch included, as
+ *   torch.max(volume); NaN when any element is NaN.  Two launches (per-block partials into work, then
+ *   one block folds them), no floating-point atomics, deterministic.  work: a caller's scratch of
+ *   work_floats >= 1 floats; min(work_floats, 1024, ceil(count / 4096)) partials are used, every one
+ *   written before it is read. */
+int sa_volume_peak(const float *volume, long count, float *peak, float *work, long work_floats, void *stream);
+/* sa_volume_stage: out = truncate(augment(volume)) in one pass.
+ *   m(b,h,j) = mde[b,h,j] lies in bin `bin` of `nbins` half-open bins, bin n holding
+ *     n/nbins <= x < (n+1)/nbins (generate_masks, utils.py:48-54: 1.0, negative values and NaN are in
+ *     no bin)
+ *   SA_VOLAUG_NONE:  c = v
+ *   SA_VOLAUG_ROLL:  c[b,h,j,k] = m ? v[b,h,(j - shift) mod W1,k] : v[b,h,j,k]   (torch.roll, dims=3;
+ *                    shift in 1..W1, shift == W1 is the identity)
+ *   SA_VOLAUG_NOISE: c = m ? v noise[b,h,j] : v
+ *   SA_VOLAUG_ZERO:  c = m ? v (peak[0] exp(-(j - k)^2 / 2)) : v   (gauss_corr_volume_naive(zeros,
+ *                    gauss_k = peak), utils.py:200-214, the curve formed first; peak is a device
+ *                    pointer, sa_volume_peak's output; W1 == W2)
+ *   then, if trunc_disp != NULL (with trunc_conf; W1 == W2):
+ *     out = c ((1 - t) + t (sigmoid((j - d) - k) (1 - atten) + atten)),  d = trunc_disp[b,h,j],
+ *     t = trunc_conf[b,h,j]: sa_corr_volume_pyramid's factor with 1 / (1 + expf(-x)) as the sigmoid;
+ *   else out = c.
+ * The selected value is written, not the reference's blend v (1 - m) + src m (equal for finite v).
+ * mde is needed unless kind is SA_VOLAUG_NONE, noise by _NOISE, peak by _ZERO.  out may alias volume
+ * for every kind but SA_VOLAUG_ROLL, which is refused when the two overlap.  Refused before any launch:
+ * null pointers, non-positive sizes or more than 2^31 - 1 rows, an unknown kind, bin outside
+ * 0..nbins-1 (nbins 1..64), shift outside 1..W1, W1 != W2 where required. */
+enum { SA_VOLAUG_NONE = 0, SA_VOLAUG_ROLL = 1, SA_VOLAUG_NOISE = 2, SA_VOLAUG_ZERO = 3 };
+int sa_volume_stage(const float *volume, int B, int H, int W1, int W2, int kind, const float *mde, int nbins,
+                    int bin, int shift, const float *noise, const float *peak, const float *trunc_disp,
+                    const float *trunc_conf, float atten, float *out, void *stream);
+/* Adjoint of the truncation multiply with respect to the volume: grad_volume = grad_out factor, the
+ * factor recomputed from the two maps by the forward's own kernel (nothing volume-sized is saved);
+ * grad_volume may alias grad_out; deterministic.  W1 == W2. */
+int sa_volume_truncate_backward(const float *grad_out, int B, int H, int W1, int W2, const float *trunc_disp,
+                                const float *trunc_conf, float atten, float *grad_volume, void *stream);
+
 /* Live per-kernel timing for bench.py: when enabled, every launch of kernel `id`
  * is bracketed by hipEvents on the launch stream; sa_timing_read synchronises the
  * recorded events and returns their summed duration (ms) and count, then clears. */

@@ -19,6 +19,7 @@
 // bytes), then write level 0 and build levels 1..3 with lane shuffles: the accumulator
 // column is the lane (col = lane&31), so pairs (k, k+1) sit in lanes (l, l^1).
 #include "sa_common.h"
+#include "volume_common.h"
 
 namespace {
 
@@ -140,11 +141,7 @@ __global__ __launch_bounds__(256) void corr_pyramid_kernel(
           d = tdisp[pix];
           m = tconf[pix];
         }
-        const float center = (float)j - d;
-        const float tv = center - (float)k;
-        const float s = sa::sigmoidf_ref(tv);
-        const float T = 1.0f * (1.0f - m) + m * (s * (1.0f - atten) + atten);
-        v = T * v;
+        v = sa::trunc_factor<false>(j, k, d, m, atten) * v;
       }
       float *row_ptr = pyr + (((long)b * g.H + h) * g.W1 + j) * g.rs;
       if (jok && k < g.W2) row_ptr[k] = v;
@@ -310,11 +307,7 @@ __global__ __launch_bounds__(256, (SHEAR ? 3 : 4)) void corr_pyramid_v2_kernel(c
   auto cell = [&](int gg, int i, int t, int j, int P, float dji, float mji) __attribute__((always_inline)) {
     float x = POW2 ? acc[gg][t][i] * inv_c : acc[gg][t][i] / sqrt_c;
     if (TRUNC) {
-      const float center = (float)j - dji;
-      const float tv = center - (float)(P + t);
-      const float s = sa::sigmoidf_fast(tv);
-      const float T = 1.0f * (1.0f - mji) + mji * (s * (1.0f - atten) + atten);
-      x = T * x;
+      x = sa::trunc_factor<true>(j, P + t, dji, mji, atten) * x;
     }
     return x;
   };

@@ -14,6 +14,7 @@
 // the final up-cat conv, conv3d_fused.hip) evaluate the one-hot cells from per-pixel
 // records (sa_mono_bin_records); the volume remains for the unfused (torch) hourglass.
 #include "sa_common.h"
+#include "volume_common.h"
 
 namespace {
 
@@ -38,13 +39,7 @@ __global__ __launch_bounds__(256) void normals_kernel(const float *__restrict__ 
   o[2 * hw] = nz / norm;
 }
 
-__device__ __forceinline__ int depth_bin(float m, int nbins) {
-  // m*nbins is exact for power-of-two nbins; the general case compares like the reference
-  for (int n = 0; n < nbins; ++n) {
-    if (m < (float)(n + 1) / (float)nbins && m >= (float)n / (float)nbins) return n;
-  }
-  return -1;
-}
+using sa::depth_bin;   // volume_common.h
 
 // one thread = VEC consecutive j of one (b, k, h): VEC-wide stores into each of the nbins
 // planes (VEC = 4 when W1 % 4 == 0, else 1)

@@ -23,13 +23,20 @@ band is empty: the forward takes its minimum-norm / zero branch there, and the r
 ``lstsq`` assumes full rank, so there is nothing to match.  The band thresholds are constants, as in
 the reference, which only compares against them.
 
+``volume_stage`` is the stage between the aggregated volumes and the two ``corr_block(...)``
+constructors of the training forward (stereoanywhere.py:214-255): ``draw_volume_corruption`` makes the
+reference's draws, ``corrupt_volume`` applies one volume-corruption branch (detached, as the reference
+detaches it) and ``truncate_volume`` is the truncation multiply, differentiable with respect to the
+volume and saving the two maps its factor is recomputed from (csrc/volume_stage.hip).
+
 Floating inputs that are not fp32 (fp16 / bf16 activations under ``torch.autocast``) are cast with
 ``.float()``: a torch op, so the gradient arrives at the caller's tensor in its own dtype.  There is
 no CPU path.
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence
+import random
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -281,3 +288,151 @@ def weighted_lsq(mde, disp, conf, min_quantile=0.2, max_quantile=0.9):
     else:
         scale, shift = ops.weighted_lsq(m, d, c, float(min_quantile), float(max_quantile))
     return scale.reshape(B, 1, 1, 1).to(mde.dtype), shift.reshape(B, 1, 1, 1).to(mde.dtype)
+
+
+# ------------------------------------------------------------------------------- volume stage
+class VolumeCorruption(NamedTuple):
+    """One drawn volume-corruption augmentation (stereoanywhere.py:217-251): which volume, which
+    branch, the depth bin of the left mono map it acts in and, for a roll, the shift along W1."""
+    target: str   # "stereo" | "mono"
+    kind: str     # "roll" | "noise" | "zero"
+    bin: int
+    shift: int    # 1..w_lowres for a roll, else 0
+
+
+_BRANCHES = tuple((t, k) for t in ("stereo", "mono") for k in ("roll", "noise", "zero"))
+
+
+def draw_volume_corruption(prob: float, n_masks: int, w_lowres: int, rng=random) -> Optional[VolumeCorruption]:
+    """The reference's draws at stereoanywhere.py:218-251 in their order: one ``rng.random()`` per
+    branch until one fires (``< prob``), then ``rng.randint(0, n_masks - 1)`` for the bin and, for a
+    roll, ``rng.randint(1, w_lowres)`` for the shift.  None when no branch fires (six draws).  rng: the
+    ``random`` module or a ``random.Random``; seeded like the reference's it gives the reference's plan."""
+    for target, kind in _BRANCHES:
+        if rng.random() < prob:
+            bin_ = rng.randint(0, n_masks - 1)
+            shift = rng.randint(1, w_lowres) if kind == "roll" else 0
+            return VolumeCorruption(target, kind, bin_, shift)
+    return None
+
+
+def _stage_volume(v: torch.Tensor, name: str) -> torch.Tensor:
+    _on_gpu(v, name)
+    if v.dim() != 5 or v.shape[1] != 1:
+        raise RuntimeError(f"{name} must be [B,1,H,W1,W2], got {tuple(v.shape)}")
+    return v.float().contiguous()
+
+
+def _stage_map(t: torch.Tensor, name: str, vol: torch.Tensor) -> torch.Tensor:
+    """A per-left-pixel map of the volume: [B,1,H,W1] (or [B,1,H,W1,1], the reference's unsqueezed form)."""
+    _on_gpu(t, name)
+    B, _, H, W1, _ = vol.shape
+    if tuple(t.shape) not in ((B, 1, H, W1), (B, 1, H, W1, 1)):
+        raise RuntimeError(f"{name} must be [B,1,H,W1] = {(B, 1, H, W1)} for a volume {tuple(vol.shape)}, "
+                           f"got {tuple(t.shape)}")
+    return t.detach().float().contiguous()
+
+
+def _check_plan(plan: VolumeCorruption, n_masks: int, vol: torch.Tensor) -> None:
+    if plan.kind not in ("roll", "noise", "zero"):
+        raise RuntimeError(f"volume corruption kind must be 'roll', 'noise' or 'zero', got {plan.kind!r}")
+    if plan.target not in ("stereo", "mono"):
+        raise RuntimeError(f"volume corruption target must be 'stereo' or 'mono', got {plan.target!r}")
+    if not 0 <= plan.bin < n_masks:
+        raise RuntimeError(f"volume corruption bin must be 0..{n_masks - 1}, got {plan.bin}")
+    if plan.kind == "roll" and not 1 <= plan.shift <= vol.shape[3]:
+        raise RuntimeError(f"volume corruption shift must be 1..W1 = {vol.shape[3]}, got {plan.shift}")
+    if plan.kind == "zero" and vol.shape[3] != vol.shape[4]:
+        raise RuntimeError(f"the 'zero' corruption needs W1 == W2, got a volume {tuple(vol.shape)}")
+
+
+def _truncation(truncate, vol: torch.Tensor):
+    disp, conf, atten = truncate
+    if vol.shape[3] != vol.shape[4]:
+        raise RuntimeError(f"the truncation needs W1 == W2, got a volume {tuple(vol.shape)}")
+    return _stage_map(disp, "disp_left", vol), _stage_map(conf, "conf_left", vol), float(atten)
+
+
+def _stage_launch(vol, mde, plan, noise, n_masks, trunc):
+    """One sa_volume_stage launch (plus sa_volume_peak's two for "zero") -> a new tensor."""
+    kw = {}
+    if plan is not None:
+        _check_plan(plan, n_masks, vol)
+        if mde is None:
+            raise RuntimeError("a volume corruption needs mde_lowres [B,1,H,W1]")
+        kw = dict(kind=plan.kind, mde=_stage_map(mde, "mde_lowres", vol), nbins=n_masks, bin=plan.bin,
+                  shift=plan.shift if plan.kind == "roll" else 1)
+        if plan.kind == "noise":
+            if noise is None:   # the reference's rand_like of its fp16 mask: the same generator draws
+                B, _, H, W1, _ = vol.shape
+                noise = torch.rand((B, 1, H, W1, 1), dtype=torch.float16, device=vol.device)
+            kw["noise"] = _stage_map(noise, "noise", vol)
+        elif plan.kind == "zero":
+            kw["peak"] = ops.volume_peak(vol)
+    if trunc is not None:
+        kw.update(trunc_disp=trunc[0], trunc_conf=trunc[1], atten=trunc[2])
+    return ops.volume_stage(vol, **kw)
+
+
+def corrupt_volume(volume, mde_lowres, plan: VolumeCorruption, noise=None, n_masks: int = 4) -> torch.Tensor:
+    """One branch of the reference's volume-corruption augmentations (stereoanywhere.py:217-251) on
+    volume [B,1,H,W1,W2]: inside depth bin ``plan.bin`` of ``n_masks`` (``vol_aug_n_masks``) of the left
+    mono map mde_lowres [B,1,H,W1] the volume is rolled by ``plan.shift`` along W1, multiplied by a
+    per-pixel noise, or multiplied by max(volume) * exp(-(j - k)^2 / 2); elsewhere it is copied.  One
+    launch (three for "zero": the maximum stays on the device).  Returns a new, detached fp32 tensor,
+    as the reference detaches these results.  noise ("noise" only): [B,1,H,W1,1] fp16 or fp32; None
+    draws ``torch.rand(..., dtype=float16)``, the reference's ``rand_like`` of its fp16 mask."""
+    vol = _stage_volume(volume, "volume").detach()
+    if plan is None:
+        raise RuntimeError("corrupt_volume: plan is None (draw_volume_corruption drew no branch)")
+    return _stage_launch(vol, mde_lowres, plan, noise, n_masks, None)
+
+
+class _TruncateFn(torch.autograd.Function):
+    """ops.volume_stage's truncation with ops.volume_truncate_backward as its adjoint.  Saves the two
+    maps; the factor is recomputed.  The maps get no gradient (the reference detaches the mask)."""
+
+    @staticmethod
+    def forward(ctx, volume, disp, conf, atten):
+        ctx.save_for_backward(disp, conf)
+        ctx.atten = atten
+        return ops.volume_stage(volume, trunc_disp=disp, trunc_conf=conf, atten=atten)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        disp, conf = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        return ops.volume_truncate_backward(grad.float().contiguous(), disp, conf, ctx.atten), None, None, None
+
+
+def truncate_volume(volume, disp_left, conf_left, attenuation_gain: float = 0.9) -> torch.Tensor:
+    """``truncate_corr_volume_v2(disp_left, conf_left, conf_th=None, attenuation_gain).detach() * volume``
+    (stereoanywhere.py:203, 253-254) in one launch: volume [B,1,H,W,W], maps [B,1,H,W].  Differentiable
+    with respect to the volume only."""
+    vol = _stage_volume(volume, "volume")
+    disp, conf, atten = _truncation((disp_left, conf_left, attenuation_gain), vol)
+    if _wants_grad(vol):
+        return _TruncateFn.apply(vol, disp, conf, atten)
+    return ops.volume_stage(vol, trunc_disp=disp, trunc_conf=conf, atten=atten)
+
+
+def volume_stage(stereo, mono, mde_lowres=None, plan: Optional[VolumeCorruption] = None, truncate=None, noise=None,
+                 n_masks: int = 4):
+    """What stands between the aggregated volumes and the two ``corr_block(...)`` constructors
+    (stereoanywhere.py:214-255) -> (stereo_out, mono_out).  plan: ``draw_volume_corruption``'s result;
+    truncate: (disp_left, conf_left, attenuation_gain) or None (``use_truncate_vol`` off).  A corrupted
+    stereo volume gets its corruption and its truncation in one launch and is detached; an uncorrupted
+    one goes through ``truncate_volume`` and keeps its ``grad_fn``.  A volume nothing touches is
+    returned as the same tensor."""
+    if plan is not None and plan.target == "mono":
+        mono = corrupt_volume(mono, mde_lowres, plan, noise, n_masks)
+        plan = None
+    if plan is not None:
+        vol = _stage_volume(stereo, "stereo").detach()
+        trunc = None if truncate is None else _truncation(truncate, vol)
+        stereo = _stage_launch(vol, mde_lowres, plan, noise, n_masks, trunc)
+    elif truncate is not None:
+        stereo = truncate_volume(stereo, *truncate)
+    return stereo, mono

@@ -349,6 +349,87 @@ def convex_upsample_backward(flow_x: torch.Tensor, mask: torch.Tensor, grad_out:
     return g_flow, g_mask
 
 
+# ------------------------------------------------------------------------------- volume stage
+VOLAUG = {k: N.CONST["SA_VOLAUG_" + k.upper()] for k in ("none", "roll", "noise", "zero")}
+_PEAK_PARTS = 1024   # partial maxima sa_volume_peak can use
+
+
+def _stage_dims(volume: torch.Tensor, name: str, who: str) -> Tuple[int, int, int, int]:
+    _check(volume, name)
+    if volume.dim() != 5 or volume.shape[1] != 1:
+        raise RuntimeError(f"{who}: {name} must be [B,1,H,W1,W2], got {tuple(volume.shape)}")
+    B, _, H, W1, W2 = volume.shape
+    return B, H, W1, W2
+
+
+def _stage_map(t: Optional[torch.Tensor], name: str, dims, who: str) -> Optional[int]:
+    """Pointer of a per-left-pixel map: contiguous fp32 [B,H,W1], [B,1,H,W1] or [B,1,H,W1,1]."""
+    if t is None:
+        return None
+    _check(t, name)
+    B, H, W1, _ = dims
+    if tuple(t.shape) not in ((B, H, W1), (B, 1, H, W1), (B, 1, H, W1, 1)):
+        raise RuntimeError(f"{who}: {name} must be [B,1,H,W1] = {(B, 1, H, W1)} (or [B,H,W1] / [B,1,H,W1,1]), "
+                           f"got {tuple(t.shape)}")
+    return t.data_ptr()
+
+
+def volume_peak(volume: torch.Tensor) -> torch.Tensor:
+    """torch.max(volume) of a contiguous fp32 tensor as a one-element device tensor (NaN when any
+    element is NaN): two launches on the current stream, no host read."""
+    _check(volume, "volume")
+    if volume.numel() == 0:
+        raise RuntimeError("volume_peak: volume is empty")
+    work = torch.empty((_PEAK_PARTS + 1,), device=volume.device, dtype=torch.float32)
+    N.call("sa_volume_peak", volume.data_ptr(), volume.numel(), work[_PEAK_PARTS:].data_ptr(), work.data_ptr(),
+           _PEAK_PARTS, _stream(volume))
+    return work[_PEAK_PARTS:]
+
+
+def volume_stage(volume: torch.Tensor, kind: str = "none", mde: Optional[torch.Tensor] = None, nbins: int = 1,
+                 bin: int = 0, shift: int = 1, noise: Optional[torch.Tensor] = None,
+                 peak: Optional[torch.Tensor] = None, trunc_disp: Optional[torch.Tensor] = None,
+                 trunc_conf: Optional[torch.Tensor] = None, atten: float = 0.9,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One launch of sa_volume_stage: the augmentation `kind` ("none", "roll", "noise", "zero") inside bin
+    `bin` of `nbins` of the left mono map `mde`, then the truncation multiply when trunc_disp /
+    trunc_conf are given.  volume [B,1,H,W1,W2] contiguous fp32; maps [B,1,H,W1]; peak: volume_peak's
+    output.  out may be the volume itself except for "roll"."""
+    if kind not in VOLAUG:
+        raise RuntimeError(f"volume_stage: kind must be one of {sorted(VOLAUG)}, got {kind!r}")
+    dims = _stage_dims(volume, "volume", "volume_stage")
+    if out is None:
+        out = torch.empty_like(volume)
+    elif _stage_dims(out, "out", "volume_stage") != dims:
+        raise RuntimeError(f"volume_stage: out must have the volume's shape {tuple(volume.shape)}, got {tuple(out.shape)}")
+    if peak is not None:
+        _check(peak, "peak")
+    ptrs = [_stage_map(t, nm, dims, "volume_stage") for t, nm in
+            ((mde, "mde"), (noise, "noise"), (trunc_disp, "trunc_disp"), (trunc_conf, "trunc_conf"))]
+    N.call("sa_volume_stage", volume.data_ptr(), *dims, VOLAUG[kind], ptrs[0], int(nbins), int(bin), int(shift),
+           ptrs[1], _ptr(peak), ptrs[2], ptrs[3], float(atten), out.data_ptr(), _stream(volume))
+    return out
+
+
+def volume_truncate_backward(grad_out: torch.Tensor, trunc_disp: torch.Tensor, trunc_conf: torch.Tensor,
+                             atten: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Adjoint of the truncation multiply with respect to the volume: grad_out [B,1,H,W,W] times the
+    factor recomputed from the two maps.  out may be grad_out itself.  Deterministic."""
+    dims = _stage_dims(grad_out, "grad_out", "volume_truncate_backward")
+    if out is None:
+        out = torch.empty_like(grad_out)
+    elif _stage_dims(out, "out", "volume_truncate_backward") != dims:
+        raise RuntimeError(f"volume_truncate_backward: out must have grad_out's shape {tuple(grad_out.shape)}, "
+                           f"got {tuple(out.shape)}")
+    if trunc_disp is None or trunc_conf is None:
+        raise RuntimeError("volume_truncate_backward: trunc_disp and trunc_conf must be given")
+    d, c = (_stage_map(t, nm, dims, "volume_truncate_backward") for t, nm in
+            ((trunc_disp, "trunc_disp"), (trunc_conf, "trunc_conf")))
+    N.call("sa_volume_truncate_backward", grad_out.data_ptr(), *dims, d, c, float(atten), out.data_ptr(),
+           _stream(grad_out))
+    return out
+
+
 def _lookup_bytes(npix: int, nvol: int, num_levels: int, radius: int, cout: int) -> float:
     """Algorithmic bytes of one fused lookup: per pixel the coordinate, per volume the 2r + 2 cells
     of each level's window and the cout output planes."""
