@@ -26,13 +26,20 @@
 
 namespace {
 
-using sa::f32x4, sa::f32x2, sa::f16x2, sa::f16x4;
+using sa::f32x4, sa::f32x2, sa::f16x2, sa::f16x4, sa::f16x8;
 
 // Split products (SP, sa_conv_direct_split): the weights are f16 (hi, lo) pairs of w * 2^12 in
 // one dword each (sa_conv_direct_weights_split), the patch values are split in registers, and
-// each v_mfma_f32_16x16x4_f32 becomes one v_mfma_f32_16x16x16_f16 over the four products
-// hi*bhi + hi*blo + lo*bhi + lo*blo (A = (hi, hi, lo, lo), B = (bhi, blo, bhi, blo)): exact
-// products, fp32 accumulation, half the MFMA cycles (as conv2d_wino4.hip's W4Split).
+// the four products hi*bhi + hi*blo + lo*bhi + lo*blo of a K-step take the place of its
+// v_mfma_f32_16x16x4_f32: exact products, fp32 accumulation (as conv2d_wino4.hip's W4Split).
+// K-steps 2j and 2j + 1 of the chunk share one v_mfma_f32_16x16x32_f16 (the full-rate f16 form:
+// twice the K of 16x16x16 at about the same issue time):
+//   A = (hi0, hi0, lo0, lo0, hi1, hi1, lo1, lo1)      two dsplit results, 3 VALU per patch value
+//   B = (bhi0, blo0, bhi0, blo0, bhi1, blo1, bhi1, blo1)   the two weight dwords, each twice
+// for the conv and (over the centre tap's steps) the downsample accumulators alike.  KC = 8 gives
+// an even number of steps per tap; the 7x7 stem's 49 steps end in one v_mfma_f32_16x16x16_f16
+// (A = (hi, hi, lo, lo), B = (bhi, blo, bhi, blo)).  The weight image, in memory and in LDS, is
+// the one of the unpaired form.
 constexpr float DSP_SCALE = 4096.0f;
 __device__ __forceinline__ f16x4 dsplit(const float x) {
   const f16x2 hh = __builtin_convertvector(f32x2{x, x}, f16x2);
@@ -73,6 +80,7 @@ struct DCfg {
   static constexpr int NACC = NTL * (DS ? 2 : 1);
   static constexpr int SMEM = XN + WROWS * NCP + 4;   // + a spare float4 for slot-less commits
   static_assert(KC % 4 == 0, "a K-step of 4 must stay inside one tap");
+  static_assert(!DS || KC % 8 == 0, "the split path's K-step pairs share the centre tap's downsample step");
   static_assert((WN + DN) % 4 == 0, "weights are staged as float4");
   static_assert(SMEM * 4 <= 160 * 1024, "LDS budget");
   static_assert(8 * 2 * NACC * 16 * 2 <= SMEM, "the stats reduction reuses the staging LDS");
@@ -168,13 +176,22 @@ __global__ __launch_bounds__(512, DS ? 2 : 4) void conv_direct_kernel(const DirA
       for (int j = 0; j < C::XPT; ++j) kr[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(kin, xoff[j], xs, 0));
       if (tid < 2 * KC) {
         const int c = min(chunk * KC + tid % KC, a.Cin - 1);
-        tv = (tid < KC ? a.cm : a.cs)[(long)n * a.Cin + c];
+        if constexpr (SP) {   // (no per-lane pointer held across the loop)
+          if (tid < KC) tv = a.cm[(long)n * a.Cin + c];
+          else tv = a.cs[(long)n * a.Cin + c];
+        } else {
+          tv = (tid < KC ? a.cm : a.cs)[(long)n * a.Cin + c];
+        }
       }
     }
 #pragma unroll
     for (int j = 0; j < C::WPT; ++j) {
-      const auto v = wds[j] ? __builtin_amdgcn_raw_buffer_load_b128(din, woff[j], chunk * C::DN * 4, 0)
-                            : __builtin_amdgcn_raw_buffer_load_b128(win, woff[j], chunk * C::WN * 4, 0);
+      // a slot whose 512 float4 are all conv rows: the lane offset of slot 0 and a scalar offset
+      // (no register per slot; the split path, which needs them for its paired operands)
+      const bool conv_rows = SP && 512 * j + 511 < C::WN / 4;
+      const auto v = conv_rows ? __builtin_amdgcn_raw_buffer_load_b128(win, woff[0], chunk * C::WN * 4 + 512 * 16 * j, 0)
+                     : wds[j]  ? __builtin_amdgcn_raw_buffer_load_b128(din, woff[j], chunk * C::DN * 4, 0)
+                               : __builtin_amdgcn_raw_buffer_load_b128(win, woff[j], chunk * C::WN * 4, 0);
       wr[j] = f32x4{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
     }
   };
@@ -218,8 +235,37 @@ __global__ __launch_bounds__(512, DS ? 2 : 4) void conv_direct_kernel(const DirA
 #pragma unroll 1
   for (int chunk = 0; chunk < a.nchunks; ++chunk) {
     if (chunk + 1 < a.nchunks) fetch(chunk + 1);
+    if constexpr (SP) {
+      // K-steps 2p and 2p + 1 on one v_mfma_f32_16x16x32_f16: a lane's k = 0..3 are step 2p's four
+      // products, k = 4..7 step 2p + 1's
 #pragma unroll
-    for (int s = 0; s < C::KSTEPS; ++s) {
+      for (int p = 0; p < C::KSTEPS / 2; ++p) {
+        const int s0 = 2 * p, s1 = 2 * p + 1;
+        const int tap0 = (4 * s0) / KC, tap1 = (4 * s1) / KC, c0 = (4 * s0) % KC, c1 = (4 * s1) % KC;
+        const int koff0 = c0 * PLANE + (tap0 / K) * PWP + (tap0 % K);
+        const int koff1 = c1 * PLANE + (tap1 / K) * PWP + (tap1 % K);
+        f16x8 a8[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+          a8[m] = __builtin_shufflevector(dsplit(sx[abase[m] + koff0]), dsplit(sx[abase[m] + koff1]), 0, 1, 2, 3, 4,
+                                          5, 6, 7);
+        auto prod2 = [&](const float b0, const float b1, f32x4 *ac) __attribute__((always_inline)) {
+          const f16x8 b = __builtin_bit_cast(f16x8, f32x4{b0, b0, b1, b1});
+#pragma unroll
+          for (int m = 0; m < MT; ++m) ac[m * C::NACC] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a8[m], b, ac[m * C::NACC], 0, 0, 0);
+        };
+#pragma unroll
+        for (int t = 0; t < NTL; ++t) prod2(sw[bbase + 4 * s0 * NCP + t * 16], sw[bbase + 4 * s1 * NCP + t * 16], &acc[0][t]);
+        if (DS && tap0 == (K / 2) * K + K / 2) {   // (KC % 8 == 0: a pair stays inside one tap)
+#pragma unroll
+          for (int t = 0; t < NTL; ++t) prod2(sd[bbase + c0 * NCP + t * 16], sd[bbase + c1 * NCP + t * 16], &acc[0][NTL + t]);
+        }
+      }
+    }
+    // fp32 products: every K-step; split products: the odd last step of the 7x7 stem's 49 (one
+    // 16x16x16 MFMA: no zero step to stage, every LDS offset still an immediate)
+#pragma unroll
+    for (int s = SP ? C::KSTEPS / 2 * 2 : 0; s < C::KSTEPS; ++s) {
       const int tap = (4 * s) / KC, ci0 = (4 * s) % KC;
       const int koff = ci0 * PLANE + (tap / K) * PWP + (tap % K);
       float av[MT];
