@@ -6,10 +6,7 @@
 //
 //   out[b][co][p] = scale * (bias[co] + sum_ci W[co][ci] x[b][ci][p])     (p over the flat H*W plane)
 //
-// Products: each fp32 product w * x as hi(w) hi(x) + hi(w) lo(x) + lo(w) hi(x) of f16 pairs (x = hi
-// + lo exactly in fp32, 22 significant bits per operand; the dropped lo * lo term is below 2^-22 of
-// the product) on v_mfma_f32_16x16x32_f16, fp32 accumulation.  Weights are scaled by 2^12 before the
-// split (exact; the accumulators are scaled back) so their lo halves stay normal f16.
+// Products: split f16 pairs on v_mfma_f32_16x16x32_f16, weights pre-scaled by 2^12 (split_f16.h).
 //
 //   block = 4 waves, 64 output channels x 128 pixels; wave = 64 channels x 32 pixels: 4 x 2 MFMA
 //           tiles (D[m = channel][n = pixel]), 32 fp32 accumulators
@@ -24,7 +21,7 @@
 //           run on one XCD and share its L2 copy of the tile's x
 //   range guard: an input of magnitude >= 65504 (f16 overflow) makes the block recompute its
 //           outputs with fp32 FMAs (exact products, the reference's arithmetic up to summation order)
-#include "sa_common.h"
+#include "conv1x1_core.h"
 
 #include <cstdint>
 
@@ -35,7 +32,6 @@ using sa::f32x4, sa::f16x2, sa::f16x8;
 constexpr int C1_CO = 64, C1_PX = 128, C1_K = 32, C1_THR = 256;
 constexpr int C1_PITCH = 132;   // floats per LDS row (128 pixels + 4: the operand reads' rows 8 apart start
                                 // 32 banks apart, so a ds_read_b32 of 16 pixels x 4 k-groups is 2-way)
-constexpr float C1_WSCALE = 4096.0f;
 
 __device__ unsigned g_c1_redo_blocks;
 
@@ -116,18 +112,14 @@ __global__ __launch_bounds__(C1_THR, 2) void conv1x1_kernel(const float *__restr
       for (int j = 0; j < 8; ++j) v[j] = xs[(bk + j) * C1_PITCH + bp + 16 * q];
       f16x8 bh, bl;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
+      for (int j = 0; j < 8; ++j) {   // (sa::split_f16_guarded, written out)
         const _Float16 h = (_Float16)v[j];
         bh[j] = h;
-        bl[j] = (_Float16)(v[j] - (float)h);   // exact in fp32
-        bad |= !(__builtin_fabsf(v[j]) < 65504.0f);
+        bl[j] = (_Float16)(v[j] - (float)h);
+        bad |= !(__builtin_fabsf(v[j]) < sa::kF16Max);
       }
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        acc[c][q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[c], bh, acc[c][q], 0, 0, 0);
-        acc[c][q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[c], bl, acc[c][q], 0, 0, 0);
-        acc[c][q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[c], bh, acc[c][q], 0, 0, 0);
-      }
+      for (int c = 0; c < 4; ++c) sa::mfma_split3(acc[c][q], wh[c], wl[c], bh, bl);
     }
     if (kc + 2 < nchunks) load_w((kc + 2) * C1_K, wh, wl);
   };
@@ -150,7 +142,7 @@ __global__ __launch_bounds__(C1_THR, 2) void conv1x1_kernel(const float *__restr
           const int co = co0 + 16 * c + dm + i;
           if (co < Cout && p < P) {
             const float bv = bias ? bias[co] : 0.0f;
-            ob[(long)co * P + p] = (acc[c][q][i] * (1.0f / C1_WSCALE) + bv) * scale;
+            ob[(long)co * P + p] = (acc[c][q][i] * (1.0f / sa::kSplitScale) + bv) * scale;
           }
         }
       }
@@ -163,8 +155,8 @@ __global__ __launch_bounds__(C1_THR, 2) void conv1x1_kernel(const float *__restr
     const long p = p0 + e % C1_PX;
     if (co >= Cout || p >= P) continue;
     float s = 0.0f;
-    for (int k = 0; k < Cin; ++k) {
-      const float w = ((float)whi[(long)co * Cin + k] + (float)wlo[(long)co * Cin + k]) * (1.0f / C1_WSCALE);
+    for (int k = 0; k < Cin; ++k) {   // (the redo dot product, as in conv1x1_v2_kernel and mask_upsample_kernel)
+      const float w = sa::split_weight_f32(whi[(long)co * Cin + k], wlo[(long)co * Cin + k]);
       s = fmaf(w, xb[(long)k * P + p], s);
     }
     ob[(long)co * P + p] = (s + (bias ? bias[co] : 0.0f)) * scale;
@@ -221,16 +213,7 @@ __global__ __launch_bounds__(C2_THR, 2) void conv1x1_v2_kernel(const float *__re
       for (int u = 0; u < 4; ++u) {
         const int kg = g0 + 4 * u;
         if (kg >= ngrp) break;
-        f16x8 h, l;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const _Float16 hh = (_Float16)v[u][j];
-          h[j] = hh;
-          l[j] = (_Float16)(v[u][j] - (float)hh);   // exact in fp32
-          bad |= !(__builtin_fabsf(v[u][j]) < 65504.0f);
-        }
-        *reinterpret_cast<f16x8 *>(&xh[(kg * C2_PX + (tid & 63)) * 8]) = h;
-        *reinterpret_cast<f16x8 *>(&xl[(kg * C2_PX + (tid & 63)) * 8]) = l;
+        bad = sa::c1_stage8<C2_PX>(v[u], xh, xl, kg, tid & 63, bad);
       }
     }
   }
@@ -241,8 +224,8 @@ __global__ __launch_bounds__(C2_THR, 2) void conv1x1_v2_kernel(const float *__re
       const long p = p0 + e % C2_PX;
       if (p >= P) continue;
       float s = 0.0f;
-      for (int k = 0; k < Cin; ++k) {
-        const float w = ((float)whi[(long)co * Cin + k] + (float)wlo[(long)co * Cin + k]) * (1.0f / C1_WSCALE);
+      for (int k = 0; k < Cin; ++k) {   // (the redo dot product, as in conv1x1_kernel and mask_upsample_kernel)
+        const float w = sa::split_weight_f32(whi[(long)co * Cin + k], wlo[(long)co * Cin + k]);
         s = fmaf(w, xb[(long)k * P + p], s);
       }
       ob[(long)co * P + p] = (s + (bias ? bias[co] : 0.0f)) * scale;
@@ -255,17 +238,7 @@ __global__ __launch_bounds__(C2_THR, 2) void conv1x1_v2_kernel(const float *__re
   const int npass = t1 > t0 ? (t1 - t0 + MT - 1) / MT : 0;
   constexpr int nks = NKS;   // (= Cin / 32)
   const int total = npass * nks;   // steps: (pass, 32 k)
-  // A operands of step it (clamped: the loads past the last step are unconditional, never used)
-  auto load_w = [&](int it, f16x8 (&wh)[MT], f16x8 (&wl)[MT]) __attribute__((always_inline)) {
-    it = __builtin_amdgcn_readfirstlane(min(it, max(total - 1, 0)));
-    const int ps = it / nks, ks = it - ps * nks;
-#pragma unroll
-    for (int t = 0; t < MT; ++t) {
-      const long o = (long)min(16 * (t0 + ps * MT + t) + am, Cout - 1) * Cin + ks * 32 + aq * 8;
-      wh[t] = *reinterpret_cast<const f16x8 *>(whi + o);
-      wl[t] = *reinterpret_cast<const f16x8 *>(wlo + o);
-    }
-  };
+  const sa::C1Wave wave{t0, total, Cout - 1, am, aq};
   f32x4 acc[MT][4];
 #pragma unroll
   for (int t = 0; t < MT; ++t)
@@ -289,7 +262,7 @@ __global__ __launch_bounds__(C2_THR, 2) void conv1x1_v2_kernel(const float *__re
           const long p = p0 + 16 * n + am;
           const bool ok = tile < t1 && co < Cout && p < P;
           const int off = ok ? (int)(((long)co * P + p) * 4) : 0x7ffffff0;
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (acc[t][n][i] * (1.0f / C1_WSCALE) + bv) * scale),
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (acc[t][n][i] * (1.0f / sa::kSplitScale) + bv) * scale),
                                                 orsrc, off, 0, 0);
         }
       }
@@ -298,36 +271,13 @@ __global__ __launch_bounds__(C2_THR, 2) void conv1x1_v2_kernel(const float *__re
     }
   };
   auto step = [&](int it, f16x8 (&wh)[MT], f16x8 (&wl)[MT]) __attribute__((always_inline)) {
-    const int kg = (it % nks) * 4 + aq;
-    f16x8 bh[4], bl[4];
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-      bh[n] = *reinterpret_cast<const f16x8 *>(&xh[(kg * C2_PX + 16 * n + am) * 8]);
-      bl[n] = *reinterpret_cast<const f16x8 *>(&xl[(kg * C2_PX + 16 * n + am) * 8]);
-    }
-    // product-major: an accumulator's three products are MT x 4 MFMAs apart (the same order of
-    // accumulation as the round-5 form: hi hi, hi lo, lo hi per 32 k)
-#pragma unroll
-    for (int t = 0; t < MT; ++t)
-#pragma unroll
-      for (int n = 0; n < 4; ++n) acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t], bh[n], acc[t][n], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < MT; ++t)
-#pragma unroll
-      for (int n = 0; n < 4; ++n) acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t], bl[n], acc[t][n], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < MT; ++t)
-#pragma unroll
-      for (int n = 0; n < 4; ++n) acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[t], bh[n], acc[t][n], 0, 0, 0);
-    load_w(it + 2, wh, wl);   // two steps ahead (the next set is already in flight)
-    __builtin_amdgcn_sched_barrier(0);   // (left to itself the scheduler sinks the first step's loads
-                                         // past the second step's MFMAs: both sets then wait together)
+    sa::c1_step<C2_PX, MT, 4, NKS, true>(acc, xh, xl, whi, wlo, wave, Cin, it, wh, wl);
   };
   // two register sets, each step's weights issued two steps ahead (a pass's steps unrolled: the
   // waits stay exact; nks even: the host sends Cin other than 64, 128, 256 to the round-5 form)
   f16x8 wha[MT], wla[MT], whb[MT], wlb[MT];
-  load_w(0, wha, wla);
-  load_w(1, whb, wlb);
+  sa::c1_load_w<MT, NKS, true>(whi, wlo, wave, Cin, 0, wha, wla);
+  sa::c1_load_w<MT, NKS, true>(whi, wlo, wave, Cin, 1, whb, wlb);
 #pragma unroll 1
   for (int ps = 0; ps < npass; ++ps) {
 #pragma unroll
@@ -344,10 +294,7 @@ __global__ __launch_bounds__(256) void conv1x1_weights_kernel(const float *__res
                                                               _Float16 *__restrict__ hi, _Float16 *__restrict__ lo) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float v = w[i] * C1_WSCALE;
-  const _Float16 h = (_Float16)v;
-  hi[i] = h;
-  lo[i] = (_Float16)(v - (float)h);
+  sa::split_f16(w[i] * sa::kSplitScale, hi[i], lo[i]);
 }
 
 }  // namespace

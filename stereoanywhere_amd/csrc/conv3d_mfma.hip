@@ -32,15 +32,13 @@
 // Layout [B, C, D, H, W] throughout (D = W2, W = W1), as conv3d_fused.hip.
 #include <cmath>
 
-#include "sa_common.h"
+#include "split_f16.h"
 
 #pragma clang fp contract(fast)
 
 namespace {
 
 using sa::f32x4, sa::f16x8;
-
-constexpr float kWScale = 4096.0f;   // 2^12: weights -> f16 range
 
 // 8 -> 8 and 16 -> 16: 8 waves (two per SIMD); 32 -> 32: 4 waves, one per SIMD (its 216 weight
 // VGPRs), each block one 16-channel half of the outputs (NCH = 2)
@@ -100,8 +98,8 @@ __global__ void mf_weights_kernel(const float *__restrict__ w, f16x8 *__restrict
   f16x8 hi, lo;
   for (int j = 0; j < 8; ++j) {
     float v = 0.0f;
-    if (G < C::NG && kd >= 0 && kd <= 2) v = w[((8 * cg + j) * 27 + kd * 9 + khw) * COUT + co] * kWScale;
-    const _Float16 h = (_Float16)v;
+    if (G < C::NG && kd >= 0 && kd <= 2) v = w[((8 * cg + j) * 27 + kd * 9 + khw) * COUT + co] * sa::kSplitScale;
+    const _Float16 h = (_Float16)v;   // (sa::split_f16, written out)
     hi[j] = h;
     lo[j] = (_Float16)(v - (float)h);
   }
@@ -196,9 +194,10 @@ __attribute__((amdgpu_waves_per_eu(MfCfg<CIN, COUT>::WPE, MfCfg<CIN, COUT>::WPE)
           const float2 nr = nrm[8 * jcg[k] + j];
           float v = __builtin_fmaf(x[k][j], nr.x, nr.y);
           v = fmaxf(v, v * slope);   // LeakyReLU for 0 <= slope <= 1 (NaN stays NaN)
-          const _Float16 h = (_Float16)v;
+          _Float16 h, l;
+          sa::split_f16(v, h, l);
           hi[j] = h;
-          lo[j] = (_Float16)(v - (float)h);
+          lo[j] = l;
         }
       }
       const int dst = ((p + C::RING) % C::RING) * C::SLOT + jdst[k];
@@ -270,9 +269,7 @@ __attribute__((amdgpu_waves_per_eu(MfCfg<CIN, COUT>::WPE, MfCfg<CIN, COUT>::WPE)
       const int t = kk % C::KS, k = kk / C::KS;
 #pragma unroll
       for (int u = 0; u < C::MT; ++u) {
-        acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[cur][u], bw[k][t][0], acc[u], 0, 0, 0);
-        acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[cur][u], bw[k][t][1], acc[u], 0, 0, 0);
-        acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[cur][u], bw[k][t][0], acc[u], 0, 0, 0);
+        sa::mfma_split3(acc[u], ah[cur][u], al[cur][u], bw[k][t][0], bw[k][t][1]);
       }
       // (the default schedule sinks every read next to its MFMA and waits on it)
       if (kk + 1 < NK) __builtin_amdgcn_sched_group_barrier(0x100, 2 * C::MT, 0);   // DS reads
@@ -289,7 +286,7 @@ __attribute__((amdgpu_waves_per_eu(MfCfg<CIN, COUT>::WPE, MfCfg<CIN, COUT>::WPE)
         const int w = wl + 16 * u;
         float v[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = acc[u][j] * (1.0f / kWScale);
+        for (int j = 0; j < 4; ++j) v[j] = acc[u][j] * (1.0f / sa::kSplitScale);
         if (vec && w + 3 < W) {
           *reinterpret_cast<float4 *>(o + w) = make_float4(v[0], v[1], v[2], v[3]);
 #pragma unroll

@@ -17,7 +17,7 @@
 // output plane fastest) so the weights are loaded once per block and the gate's (h, w) factors once
 // per run of planes.  InstanceNorm partials (float64) per (image, channel, tile).
 // Layout [B, C, D, H, W] (D = W2, W = W1), as conv3d_fused.hip.
-#include "sa_common.h"
+#include "split_f16.h"
 
 #pragma clang fp contract(fast)
 
@@ -25,7 +25,6 @@ namespace {
 
 using sa::f32x4, sa::f16x8;
 
-constexpr float kS2WScale = 4096.0f;                  // 2^12: weights -> f16 range
 constexpr int S2_CIN = 16, S2_COUT = 32, S2_KS = 14;  // K-steps: 2 taps x 16 channels
 constexpr int S2_TR = 4, S2_TC = 16;                  // output rows x columns per tile
 constexpr int S2_PR = 2 * S2_TR + 1, S2_PC = 2 * S2_TC + 1;   // 9 x 33 input rows x columns
@@ -44,8 +43,8 @@ __global__ void s2mf_weights_kernel(const float *__restrict__ w, f16x8 *__restri
   const int g = lane >> 4, tap = 2 * s + (g >> 1), cg = g & 1, co = 16 * nt + (lane & 15);
   f16x8 hi, lo;
   for (int j = 0; j < 8; ++j) {
-    const float v = tap < 27 ? w[((8 * cg + j) * 27 + tap) * S2_COUT + co] * kS2WScale : 0.0f;
-    const _Float16 h = (_Float16)v;
+    const float v = tap < 27 ? w[((8 * cg + j) * 27 + tap) * S2_COUT + co] * sa::kSplitScale : 0.0f;
+    const _Float16 h = (_Float16)v;   // (sa::split_f16, written out)
     hi[j] = h;
     lo[j] = (_Float16)(v - (float)h);
   }
@@ -139,7 +138,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_s2mf_kernel(const float *__rest
           v = fmaxf(v, v * slope);
           if (gl) v = gt[j] * v;
           v = ok ? v : 0.0f;
-          const _Float16 h = (_Float16)v;
+          const _Float16 h = (_Float16)v;   // (sa::split_f16, written out)
           hi[j] = h;
           lo[j] = (_Float16)(v - (float)h);
         }
@@ -164,7 +163,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_s2mf_kernel(const float *__rest
       for (int mt = 0; mt < 2; ++mt) {
         const int base = cgl * 2 * 3 * S2_PPL + pk + (2 * (2 * rh + mt) + kh) * S2_PC + m + (kw == 1 ? 17 : kw >> 1);
         const f16x8 ahi = lds[base], alo = lds[base + 3 * S2_PPL];
-        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bw[s][0], acc[mt], 0, 0, 0);
+        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bw[s][0], acc[mt], 0, 0, 0);   // (sa::mfma_split3, written out)
         acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bw[s][1], acc[mt], 0, 0, 0);
         acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bw[s][0], acc[mt], 0, 0, 0);
       }
@@ -178,7 +177,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_s2mf_kernel(const float *__rest
       if (oh >= Ho) continue;
       float v[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = acc[mt][j] * (1.0f / kS2WScale);
+      for (int j = 0; j < 4; ++j) v[j] = acc[mt][j] * (1.0f / sa::kSplitScale);
       float *dst = out + (((long)b * S2_COUT + co) * Do + od) * (long)Ho * Wo + (long)oh * Wo + ow;
       if (ow + 3 < Wo && (Wo & 3) == 0) {
         *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);

@@ -20,7 +20,7 @@
 //            relu(relu((c2 - mean) * rstd) + skip) per (image, channel) plane, formed while the
 //            patch is staged (c2 and skip loaded at the same offsets; zero padding outside the
 //            image), the arithmetic of sa_norm_act's pass exactly (no contraction)
-#include "sa_common.h"
+#include "split_f16.h"
 
 #pragma clang fp contract(fast)
 
@@ -40,7 +40,6 @@ using sa::f32x4, sa::f32x2, sa::f16x2, sa::f16x4, sa::f16x8;
 // an even number of steps per tap; the 7x7 stem's 49 steps end in one v_mfma_f32_16x16x16_f16
 // (A = (hi, hi, lo, lo), B = (bhi, blo, bhi, blo)).  The weight image, in memory and in LDS, is
 // the one of the unpaired form.
-constexpr float DSP_SCALE = 4096.0f;
 __device__ __forceinline__ f16x4 dsplit(const float x) {
   const f16x2 hh = __builtin_convertvector(f32x2{x, x}, f16x2);
   float l;
@@ -352,7 +351,7 @@ __global__ __launch_bounds__(512, DS ? 2 : 4) void conv_direct_kernel(const DirA
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
-      for (int t = 0; t < C::NACC; ++t) acc[m][t] *= 1.0f / DSP_SCALE;
+      for (int t = 0; t < C::NACC; ++t) acc[m][t] *= 1.0f / sa::kSplitScale;
   }
   // ---- epilogue: lane holds channel t*16 + (lane & 15), pixels 4*(lane>>4) + r of segment m.
   // The stats reduction reuses the staging LDS (free after the loop's last barrier).
@@ -480,7 +479,7 @@ namespace {
 __global__ void direct_split_kernel(const float *__restrict__ w, long n, unsigned *__restrict__ out) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const double u = (double)w[i] * DSP_SCALE;
+  const double u = (double)w[i] * sa::kSplitScale;
   const _Float16 hi = (_Float16)(float)u;
   const _Float16 lo = (_Float16)(float)(u - (double)hi);
   out[i] = (unsigned)__builtin_bit_cast(unsigned short, hi) | ((unsigned)__builtin_bit_cast(unsigned short, lo) << 16);

@@ -30,6 +30,7 @@
 #include <cstdint>
 
 #include "sa_common.h"
+#include "softmax9.h"
 
 namespace {
 
@@ -244,22 +245,6 @@ __global__ __launch_bounds__(256) void sab_grad_kernel(SBJob j0, SBJob j1, SBGeo
 }
 
 // ------------------------------------------------------------------------- convex up-sampling
-// softmax over the 9 taps, as upsample.hip's convex_px
-__device__ __forceinline__ void softmax9(float (&lg)[9]) {
-  float mx = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) mx = fmaxf(mx, lg[k]);
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    lg[k] = expf(lg[k] - mx);
-    s += lg[k];
-  }
-  const float inv = 1.0f / s;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) lg[k] *= inv;
-}
-
 // thread = (b, a, h, w), w fastest; F: the factor at compile time (0: f_rt)
 template <int F>
 __global__ __launch_bounds__(256) void cub_mask_kernel(const float *__restrict__ flow, const float *__restrict__ mask,
@@ -293,7 +278,7 @@ __global__ __launch_bounds__(256) void cub_mask_kernel(const float *__restrict__
     float s[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) s[k] = m[k * kstride + (long)c * hw];
-    softmax9(s);
+    sa::softmax9(s);
     float dot = 0.f;
 #pragma unroll
     for (int k = 0; k < 9; ++k) dot += s[k] * u[k];
@@ -336,7 +321,7 @@ __global__ __launch_bounds__(256) void cub_flow_kernel(const float *__restrict__
         float s[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) s[k] = m[k * kstride + (long)(a * f + c) * hw];
-        softmax9(s);
+        sa::softmax9(s);
         float st = s[0];
 #pragma unroll
         for (int k = 1; k < 9; ++k) st = k == t ? s[k] : st;   // (no run-time register index)

@@ -6,11 +6,9 @@
 //   out[b][4 h + a][4 w + c] = sum_k softmax_k(z[b][16 k + 4 a + c][h][w]) * 4 flow[b][h + k / 3 - 1][w + k % 3 - 1]
 //   z[b][co][p] = scale * (bias[co] + sum_ci W[co][ci] x[b][ci][p])        (flow zero-padded)
 //
-// Products as in conv1x1.hip (conv1x1_v2_kernel): the same pre-split weights (f16 hi / lo of
-// w * 2^12), each fp32 product as hi hi + hi lo + lo hi on v_mfma_f32_16x16x32_f16 in the same
-// order per 32 k, fp32 accumulation, the input split once as it is staged; the logits are the bits
-// sa_conv1x1 writes.  Softmax and weighted sum are convex_up_px_kernel's operations in its order
-// (upsample.hip).
+// Products as in conv1x1.hip: the same pre-split weights, and conv1x1_core.h's functions that
+// conv1x1_v2_kernel runs, so the logits are the bits sa_conv1x1 writes.  Softmax and weighted sum are
+// convex_up_px_kernel's (upsample.hip): softmax9.h's convex_px.
 //
 //   block = 3 waves, 48 consecutive pixels of one image's flat H*W plane (pixels past the plane's
 //           end are staged as zeros and never stored) for all 144 channels.  The pixels' Cin inputs
@@ -26,7 +24,8 @@
 //           output row 4 h + a (16-byte aligned whenever out and its batch stride are).
 //   range guard: an input of magnitude >= 65504 (f16 overflow) makes the block compute its logits
 //           with fp32 FMAs (as conv1x1_v2_kernel does) before the same epilogue.
-#include "sa_common.h"
+#include "conv1x1_core.h"
+#include "softmax9.h"
 
 #include <cstdint>
 
@@ -36,31 +35,8 @@ using sa::f32x4, sa::f16x8;
 
 constexpr int MU_PX = 48, MU_THR = 192, MU_CO = 144, MU_MT = 3, MU_NT = 3;
 constexpr int MU_LG_PITCH = 60;   // floats per logit row: rows 4 apart start 48 banks apart
-constexpr float MU_WSCALE = 4096.0f;
 
 __device__ unsigned g_mu_redo_blocks;
-
-// (convex_px of upsample.hip: max, exp, sum, then the weighted sum in k order)
-__device__ __forceinline__ float mu_convex_px(const float (&lg_in)[9], const float (&v)[9]) {
-  float lg[9];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    lg[k] = lg_in[k];
-    mx = fmaxf(mx, lg[k]);
-  }
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    lg[k] = expf(lg[k] - mx);
-    s += lg[k];
-  }
-  const float inv = 1.0f / s;
-  float acc = 0.f;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) acc += (lg[k] * inv) * v[k];
-  return acc;
-}
 
 constexpr int mu_lds_bytes(int nks) {
   const int xb = 2 * nks * 4 * MU_PX * 8 * 2, lb = MU_CO * MU_LG_PITCH * 4;
@@ -121,17 +97,10 @@ __global__ __launch_bounds__(MU_THR) void mask_upsample_kernel(const float *__re
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
       const int kg = ea + 4 * u;
-      f16x8 h, l;
+      float f[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float f = eok ? v[u][j] : 0.0f;
-        const _Float16 hh = (_Float16)f;
-        h[j] = hh;
-        l[j] = (_Float16)(f - (float)hh);   // exact in fp32
-        bad |= !(__builtin_fabsf(f) < 65504.0f);
-      }
-      *reinterpret_cast<f16x8 *>(&xh[(kg * MU_PX + epx) * 8]) = h;
-      *reinterpret_cast<f16x8 *>(&xl[(kg * MU_PX + epx) * 8]) = l;
+      for (int j = 0; j < 8; ++j) f[j] = eok ? v[u][j] : 0.0f;
+      bad = sa::c1_stage8<MU_PX>(f, xh, xl, kg, epx, bad);
     }
   }
   if (__syncthreads_or(bad)) {   // range guard: the block's logits with fp32 FMAs (exact products)
@@ -141,8 +110,8 @@ __global__ __launch_bounds__(MU_THR) void mask_upsample_kernel(const float *__re
       const long p = p0 + px;
       float s = 0.0f;
       if (p < P)
-        for (int k = 0; k < Cin; ++k) {
-          const float w = ((float)whi[(long)co * Cin + k] + (float)wlo[(long)co * Cin + k]) * (1.0f / MU_WSCALE);
+        for (int k = 0; k < Cin; ++k) {   // (the redo dot product, as in conv1x1.hip's two kernels)
+          const float w = sa::split_weight_f32(whi[(long)co * Cin + k], wlo[(long)co * Cin + k]);
           s = fmaf(w, xb[(long)k * P + p], s);
         }
       lgs[co * MU_LG_PITCH + px] = (s + bs[co]) * scale;
@@ -150,51 +119,19 @@ __global__ __launch_bounds__(MU_THR) void mask_upsample_kernel(const float *__re
   } else {
     const int am = lane & 15, aq = lane >> 4;   // A: channel row am of a tile, k = 8 aq .. + 7; B: pixel am of a tile
     const int t0 = __builtin_amdgcn_readfirstlane(wv) * MU_MT;
-    // A operands of 32-k step ks (clamped: the loads past the last step are unconditional, never used)
-    auto load_w = [&](int ks, f16x8 (&wh)[MU_MT], f16x8 (&wl)[MU_MT]) __attribute__((always_inline)) {
-      ks = min(ks, NKS - 1);
-#pragma unroll
-      for (int t = 0; t < MU_MT; ++t) {
-        const long o = (long)(16 * (t0 + t) + am) * Cin + ks * 32 + aq * 8;
-        wh[t] = *reinterpret_cast<const f16x8 *>(whi + o);
-        wl[t] = *reinterpret_cast<const f16x8 *>(wlo + o);
-      }
-    };
     f32x4 acc[MU_MT][MU_NT];
 #pragma unroll
     for (int t = 0; t < MU_MT; ++t)
 #pragma unroll
       for (int n = 0; n < MU_NT; ++n) acc[t][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // conv1x1_v2_kernel's pipeline: one pass of NKS steps, every tile whole
+    const sa::C1Wave wave{t0, NKS, MU_CO - 1, am, aq};
     auto step = [&](int ks, f16x8 (&wh)[MU_MT], f16x8 (&wl)[MU_MT]) __attribute__((always_inline)) {
-      const int kg = ks * 4 + aq;
-      f16x8 bh[MU_NT], bl[MU_NT];
-#pragma unroll
-      for (int n = 0; n < MU_NT; ++n) {
-        bh[n] = *reinterpret_cast<const f16x8 *>(&xh[(kg * MU_PX + 16 * n + am) * 8]);
-        bl[n] = *reinterpret_cast<const f16x8 *>(&xl[(kg * MU_PX + 16 * n + am) * 8]);
-      }
-      // product-major, conv1x1_v2_kernel's order of accumulation: hi hi, hi lo, lo hi per 32 k
-#pragma unroll
-      for (int t = 0; t < MU_MT; ++t)
-#pragma unroll
-        for (int n = 0; n < MU_NT; ++n)
-          acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t], bh[n], acc[t][n], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < MU_MT; ++t)
-#pragma unroll
-        for (int n = 0; n < MU_NT; ++n)
-          acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[t], bl[n], acc[t][n], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < MU_MT; ++t)
-#pragma unroll
-        for (int n = 0; n < MU_NT; ++n)
-          acc[t][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[t], bh[n], acc[t][n], 0, 0, 0);
-      load_w(ks + 2, wh, wl);   // two steps ahead (the next set is already in flight)
-      __builtin_amdgcn_sched_barrier(0);
+      sa::c1_step<MU_PX, MU_MT, MU_NT, NKS, false>(acc, xh, xl, whi, wlo, wave, Cin, ks, wh, wl);
     };
     f16x8 wha[MU_MT], wla[MU_MT], whb[MU_MT], wlb[MU_MT];
-    load_w(0, wha, wla);
-    load_w(1, whb, wlb);
+    sa::c1_load_w<MU_MT, NKS, false>(whi, wlo, wave, Cin, 0, wha, wla);
+    sa::c1_load_w<MU_MT, NKS, false>(whi, wlo, wave, Cin, 1, whb, wlb);
 #pragma unroll
     for (int ks = 0; ks < NKS; ks += 2) {   // (NKS even: Cin 64, 128, 256)
       step(ks, wha, wla);
@@ -210,7 +147,7 @@ __global__ __launch_bounds__(MU_THR) void mask_upsample_kernel(const float *__re
         const float bv = bs[co];
 #pragma unroll
         for (int n = 0; n < MU_NT; ++n)
-          lgs[co * MU_LG_PITCH + 16 * n + am] = (acc[t][n][i] * (1.0f / MU_WSCALE) + bv) * scale;
+          lgs[co * MU_LG_PITCH + 16 * n + am] = (acc[t][n][i] * (1.0f / sa::kSplitScale) + bv) * scale;
       }
   }
   __syncthreads();
@@ -221,10 +158,10 @@ __global__ __launch_bounds__(MU_THR) void mask_upsample_kernel(const float *__re
   for (int c = 0; c < 4; ++c)
 #pragma unroll
     for (int k = 0; k < 9; ++k) lg[c][k] = lgs[(16 * k + 4 * ea + c) * MU_LG_PITCH + epx];
-  o.x = mu_convex_px(lg[0], fv);
-  o.y = mu_convex_px(lg[1], fv);
-  o.z = mu_convex_px(lg[2], fv);
-  o.w = mu_convex_px(lg[3], fv);
+  o.x = sa::convex_px(lg[0], fv);
+  o.y = sa::convex_px(lg[1], fv);
+  o.z = sa::convex_px(lg[2], fv);
+  o.w = sa::convex_px(lg[3], fv);
   if (eok) *reinterpret_cast<float4 *>(out + (long)b * out_bs + (long)(4 * eh + ea) * (4L * W) + 4 * ew) = o;
 }
 

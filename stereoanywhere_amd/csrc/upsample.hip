@@ -10,32 +10,11 @@
 // 4 planes interleaved, and fetched ~1.3x the mask's bytes), its 36 logits all in flight together,
 // and the 4 outputs are one float4 store.  The same operations per output, in the same order:
 // bit-identical to convex_up_kernel (the other factors' path).
-#include "sa_common.h"
+#include "softmax9.h"
 
 #include <cstdint>
 
 namespace {
-
-__device__ __forceinline__ float convex_px(const float (&lg_in)[9], const float (&v)[9]) {
-  float lg[9];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    lg[k] = lg_in[k];
-    mx = fmaxf(mx, lg[k]);
-  }
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    lg[k] = expf(lg[k] - mx);
-    s += lg[k];
-  }
-  const float inv = 1.0f / s;
-  float acc = 0.f;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) acc += (lg[k] * inv) * v[k];
-  return acc;
-}
 
 __global__ __launch_bounds__(256) void convex_up_px_kernel(const float *__restrict__ flow,
                                                            const float *__restrict__ mask, long mask_bs, int H,
@@ -68,10 +47,10 @@ __global__ __launch_bounds__(256) void convex_up_px_kernel(const float *__restri
 #pragma unroll
     for (int k = 0; k < 9; ++k) lg[c][k] = m[k * kstride + (long)c * hw];
   float4 o;
-  o.x = convex_px(lg[0], v);
-  o.y = convex_px(lg[1], v);
-  o.z = convex_px(lg[2], v);
-  o.w = convex_px(lg[3], v);
+  o.x = sa::convex_px(lg[0], v);
+  o.y = sa::convex_px(lg[1], v);
+  o.z = sa::convex_px(lg[2], v);
+  o.w = sa::convex_px(lg[3], v);
   const int Wo = W * f;
   *reinterpret_cast<float4 *>(out + b * hw * f * f + (long)(h * f + a) * Wo + w * f) = o;
 }
@@ -91,27 +70,17 @@ __global__ __launch_bounds__(256) void convex_up_kernel(const float *__restrict_
   const float *m = mask + b * mask_bs + (long)(a * f + c) * hw + (long)h * W + w;
   const long kstride = (long)f * f * hw;
   float lg[9];
-  float mx = -INFINITY;
 #pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    lg[k] = m[k * kstride];
-    mx = fmaxf(mx, lg[k]);
-  }
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    lg[k] = expf(lg[k] - mx);
-    s += lg[k];
-  }
-  const float inv = 1.0f / s;
+  for (int k = 0; k < 9; ++k) lg[k] = m[k * kstride];
+  sa::softmax9(lg);
   const float *fl = flow + b * hw;
   const float ff = (float)f;
   float acc = 0.f;
 #pragma unroll
-  for (int k = 0; k < 9; ++k) {
+  for (int k = 0; k < 9; ++k) {   // (convex_px's sum, the neighbours loaded as they are used)
     const int yy = h + k / 3 - 1, xx = w + k % 3 - 1;
     const float v = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? ff * fl[(long)yy * W + xx] : 0.0f;
-    acc += (lg[k] * inv) * v;
+    acc += lg[k] * v;
   }
   out[i] = acc;
 }
