@@ -914,6 +914,39 @@ int sa_volume_stage(const float *volume, int B, int H, int W1, int W2, int kind,
 int sa_volume_truncate_backward(const float *grad_out, int B, int H, int W1, int W2, const float *trunc_disp,
                                 const float *trunc_conf, float atten, float *grad_volume, void *stream);
 
+/* The close of a training-time hourglass layer (volume_close.hip): InstanceNorm3d + LeakyReLU (+ the
+ * DoubleFeatureAtt gate; hourglass.py:61-91, submodule.py:25-53, 113-140) on a volume that any conv
+ * produced, forward statistics and backward.  Volumes are [B, C, D = W2, H, W = W1] contiguous fp32,
+ * the gates sigmoid'ed maps at the volume's resolution, gate_l [B,C,H,W] and gate_r [B,C,H,D]: the
+ * contract of sa_conv3d / sa_vol_apply.  With n = D H W, per (b, c):
+ *   xh = (x - mean) rstd,  a = lrelu(xh),  G = gate_l[h,w] gate_r[h,d],  out = G a  (out = a, no gate)
+ * The forward is sa_volume_close_stats, sa_instnorm_finalize, then sa_vol_apply (act = 1).
+ * Additive: no ABI version change; the launches are timed under SA_K_MISC.  Deterministic: no
+ * atomics, every sum in an order fixed by indices.  Refused before any launch: null pointers,
+ * non-positive sizes, D*H*W >= 2^30 or == 1 (InstanceNorm of one cell), B*C*D*H > 2^31 - 1.
+ *
+ * sa_volume_close_stats: per-block float64 (sum, sum^2) of x, [B*C][parts][2] with
+ *   parts = sa_volume_close_stat_parts(D, H, W) (-1 for a non-positive size); reduce with
+ *   sa_instnorm_finalize(partial, B*C, parts, D*H*W, eps, mean, rstd). */
+long sa_volume_close_stat_parts(int D, int H, int W);
+int sa_volume_close_stats(const float *x, int B, int C, int D, int H, int W, double *stats_partial, void *stream);
+/* sa_volume_close_backward: with g = grad_out and u = g G (xh > 0 ? 1 : slope) (torch's leaky_relu
+ *   rule: the slope at xh == 0), S1 = sum u and S2 = sum u xh over the n cells of a (b, c):
+ *     grad_x = rstd (u - S1/n - xh S2/n)
+ *     grad_gate_l[b,c,h,w] = sum_d g a gate_r[h,d],   grad_gate_r[b,c,h,d] = sum_w g a gate_l[h,w]
+ *   xh and a are recomputed from x, mean and rstd (nothing volume-sized is saved).  A reduce launch
+ *   (one block per (b, c, h): the gate gradients and float64 (S1, S2) partials), a one-wave fold per
+ *   (b, c) and the apply launch; the last two only with grad_x.  gate_l / gate_r: both or neither
+ *   (NULL: the gate-less close).  Any of grad_x, grad_gate_l, grad_gate_r may be NULL to skip it (not
+ *   all; the gate gradients need the gates).  grad_x may not overlap x or grad_out.  work: the caller's
+ *   scratch of sa_volume_close_backward_work(B, C, H) doubles (-1 for a non-positive size), every one
+ *   written before it is read. */
+long sa_volume_close_backward_work(int B, int C, int H);
+int sa_volume_close_backward(const float *x, const float *grad_out, int B, int C, int D, int H, int W,
+                             const float *mean, const float *rstd, const float *gate_l, const float *gate_r,
+                             float slope, double *work, float *grad_x, float *grad_gate_l, float *grad_gate_r,
+                             void *stream);
+
 /* Live per-kernel timing for bench.py: when enabled, every launch of kernel `id`
  * is bracketed by hipEvents on the launch stream; sa_timing_read synchronises the
  * recorded events and returns their summed duration (ms) and count, then clears. */

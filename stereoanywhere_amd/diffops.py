@@ -29,6 +29,11 @@ reference's draws, ``corrupt_volume`` applies one volume-corruption branch (deta
 detaches it) and ``truncate_volume`` is the truncation multiply, differentiable with respect to the
 volume and saving the two maps its factor is recomputed from (csrc/volume_stage.hip).
 
+``volume_close`` is the close of a training-time hourglass layer, InstanceNorm3d + LeakyReLU (+ the
+DoubleFeatureAtt gate), on a volume a torch conv produced: differentiable with respect to the volume and
+both gate maps, saving the volume, the maps and the statistics (csrc/volume_close.hip);
+``hourglass_forward`` is the reference's ``Hourglass.forward`` built on it.
+
 Floating inputs that are not fp32 (fp16 / bf16 activations under ``torch.autocast``) are cast with
 ``.float()``: a torch op, so the gradient arrives at the caller's tensor in its own dtype.  There is
 no CPU path.
@@ -436,3 +441,118 @@ def volume_stage(stereo, mono, mde_lowres=None, plan: Optional[VolumeCorruption]
     elif truncate is not None:
         stereo = truncate_volume(stereo, *truncate)
     return stereo, mono
+
+
+# ------------------------------------------------------------------------------- volume close
+class _VolumeCloseFn(torch.autograd.Function):
+    """ops.volume_close_stats + ops.vol_apply with ops.volume_close_backward as the adjoint.  Saves x, the
+    two gate maps and mean / rstd; the normalised, activated and gated volumes are recomputed."""
+
+    @staticmethod
+    def forward(ctx, x, gate_left, gate_right, slope, eps):
+        mean, rstd = ops.volume_close_stats(x, eps)
+        ctx.save_for_backward(x, gate_left, gate_right, mean, rstd)
+        ctx.slope = slope
+        gate = None if gate_left is None else (gate_left, gate_right)
+        return ops.vol_apply(ops.VolAct(x, (mean, rstd), act=True, gate=gate), slope).raw
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        x, gate_left, gate_right, mean, rstd = ctx.saved_tensors
+        need_x, need_l, need_r = ctx.needs_input_grad[:3]
+        if not (need_x or need_l or need_r):
+            return None, None, None, None, None
+        dx, dgl, dgr = ops.volume_close_backward(grad.float().contiguous(), x, mean, rstd, gate_left, gate_right,
+                                                 ctx.slope, need_x, need_l, need_r)
+        return dx, dgl, dgr, None, None
+
+
+def _close_map(t: torch.Tensor, name: str, shape) -> torch.Tensor:
+    _on_gpu(t, name)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"volume_close: {name} must be {tuple(shape)} for this volume, got {tuple(t.shape)}")
+    return t.float().contiguous()
+
+
+def volume_close(x, gate_left=None, gate_right=None, negative_slope: float = 0.01, eps: float = 1e-5) -> torch.Tensor:
+    """``gate * leaky_relu(instance_norm(x), negative_slope)``: the close of an hourglass layer
+    (submodule.py:25-53, 113-140) on a volume x [B,C,D,H,W] that any conv produced, as three streaming
+    HIP passes forward and five backward (csrc/volume_close.hip).  gate_left [B,C,H,W] and gate_right
+    [B,C,H,D] are the sigmoid'ed DoubleFeatureAtt maps at the volume's own resolution (both or neither);
+    the gate is ``gate_left[:, :, None] * gate_right.permute(0, 1, 3, 2)[..., None]``.  Differentiable
+    with respect to x and both maps (the sigmoid stays with the caller, so autograd carries the map
+    gradients on).  Instance statistics (biased variance, ``affine=False``) in every mode."""
+    _on_gpu(x, "x")
+    if x.dim() != 5:
+        raise ValueError(f"volume_close: x must be [B,C,D,H,W], got {tuple(x.shape)}")
+    if (gate_left is None) != (gate_right is None):
+        raise ValueError("volume_close: give both gate maps or neither")
+    B, C, D, H, W = x.shape
+    if D * H * W <= 1:
+        raise ValueError(f"volume_close: instance norm needs more than one cell per channel, got {tuple(x.shape)}")
+    x = x.float().contiguous()
+    if gate_left is not None:
+        gate_left = _close_map(gate_left, "gate_left", (B, C, H, W))
+        gate_right = _close_map(gate_right, "gate_right", (B, C, H, D))
+    return _VolumeCloseFn.apply(x, gate_left, gate_right, float(negative_slope), float(eps))
+
+
+def _close_layer(conv_block, x, gate=None):
+    """One BasicConv (its own nn.Conv3d on torch, then the fused close) -> its output volume."""
+    return volume_close(conv_block.conv(x), *(gate or (None, None)),
+                        negative_slope=getattr(conv_block.act_fn, "negative_slope", 0.01),
+                        eps=getattr(conv_block.norm_fn, "eps", 1e-5))
+
+
+def _close_gated(layers, att, x, feat_left, feat_right):
+    """A Sequential of BasicConvs followed by a DoubleFeatureAtt: the gate goes into the last close when
+    its maps are at the volume's resolution, else that close runs gate-less and the module's own
+    interpolate-and-multiply follows."""
+    for layer in list(layers)[:-1]:
+        x = _close_layer(layer, x)
+    y = layers[-1].conv(x)
+    gl = torch.sigmoid(att.feat_att_left(feat_left))
+    gr = torch.sigmoid(att.feat_att_right(feat_right))
+    D, H, W = y.shape[2:]
+    last = dict(negative_slope=getattr(layers[-1].act_fn, "negative_slope", 0.01),
+                eps=getattr(layers[-1].norm_fn, "eps", 1e-5))
+    if tuple(gl.shape[2:]) == (H, W) and tuple(gr.shape[2:]) == (H, D):
+        return volume_close(y, gl, gr, **last)
+    g = gl.unsqueeze(2) * gr.permute(0, 1, 3, 2).unsqueeze(4)
+    g = torch.nn.functional.interpolate(g, size=(D, H, W), mode="trilinear", align_corners=True)
+    return g * volume_close(y, **last)
+
+
+def hourglass_forward(hg, x, features_left, features_right, layout: str = "reference"):
+    """The live part of the reference's ``Hourglass.forward`` (hourglass.py:61-91) for fine-tuning: the
+    module's own ``nn.Conv3d``s on torch / MIOpen, every InstanceNorm3d + LeakyReLU (+ the following
+    DoubleFeatureAtt) as one ``volume_close``.  The deepest down layer and the first up-path step feed
+    nothing (``blocks.Hourglass``'s docstring) and are skipped, so their parameters get no gradient.
+
+    ``hg``: the reference's ``Hourglass`` or ``blocks.Hourglass`` (only ``down_layers``, ``agg_layers``,
+    ``final_agg``, ``feature_atts``, ``feature_atts_up``, ``final_feature_atts_up`` and
+    ``number_of_scales`` are used).  layout="reference" takes and returns [B,C,H,W1,W2] with the
+    reference's permutes (``types.MethodType(hourglass_forward, hg)`` replaces its forward);
+    layout="volume" works on [B,C,W2,H,W1].  Trilinear up-sampling and ``cat`` stay on torch."""
+    if layout not in ("reference", "volume"):
+        raise ValueError(f"hourglass_forward: layout must be 'reference' or 'volume', got {layout!r}")
+    interpolate = torch.nn.functional.interpolate
+    ns = hg.number_of_scales
+    if layout == "reference":
+        x = x.permute(0, 1, 3, 2, 4).permute(0, 1, 4, 3, 2)
+    orig = x
+    downs = []
+    for i in range(ns - 2):
+        x = _close_gated(hg.down_layers[i], hg.feature_atts[i], x, features_left[i + 1], features_right[i + 1])
+        downs.append(x)
+    i = ns - 3
+    up = interpolate(downs[ns - 2 - i], size=downs[ns - 3 - i].shape[2:], mode="trilinear", align_corners=True)
+    x = _close_gated(hg.agg_layers[i], hg.feature_atts_up[i], torch.cat((up, downs[ns - 3 - i]), 1),
+                     features_left[ns - 2 - i], features_right[ns - 2 - i])
+    up = interpolate(x, size=orig.shape[2:], mode="trilinear", align_corners=True)
+    x = _close_gated(hg.final_agg, hg.final_feature_atts_up, torch.cat((orig, up), 1), features_left[0],
+                     features_right[0])
+    if layout == "reference":
+        x = x.permute(0, 1, 4, 3, 2).permute(0, 1, 3, 2, 4)
+    return x

@@ -430,6 +430,76 @@ def volume_truncate_backward(grad_out: torch.Tensor, trunc_disp: torch.Tensor, t
     return out
 
 
+# ------------------------------------------------------------------------------- volume close
+def _close_dims(x: torch.Tensor, name: str, who: str) -> Tuple[int, int, int, int, int]:
+    _check(x, name)
+    if x.dim() != 5:
+        raise RuntimeError(f"{who}: {name} must be [B,C,D,H,W], got {tuple(x.shape)}")
+    return tuple(x.shape)
+
+
+def _close_gates(gate_left, gate_right, dims, who: str):
+    """Pointers of the sigmoid'ed gate maps gate_left [B,C,H,W] and gate_right [B,C,H,D] (both or neither)."""
+    if (gate_left is None) != (gate_right is None):
+        raise RuntimeError(f"{who}: gate_left and gate_right go together")
+    if gate_left is None:
+        return None, None
+    B, C, D, H, W = dims
+    _check(gate_left, "gate_left")
+    _check(gate_right, "gate_right")
+    if tuple(gate_left.shape) != (B, C, H, W) or tuple(gate_right.shape) != (B, C, H, D):
+        raise RuntimeError(f"{who}: a volume {dims} needs gate_left {(B, C, H, W)} and gate_right {(B, C, H, D)}, got "
+                           f"{tuple(gate_left.shape)} and {tuple(gate_right.shape)}")
+    return gate_left.data_ptr(), gate_right.data_ptr()
+
+
+def volume_close_stats(x: torch.Tensor, eps: float = 1e-5):
+    """InstanceNorm3d statistics of a contiguous fp32 volume [B,C,D,H,W] -> (mean, rstd), [B*C] each
+    (biased variance, rstd = 1/sqrt(var + eps)): float64 block partials (sa_volume_close_stats) folded
+    in index order by sa_instnorm_finalize.  Deterministic."""
+    B, C, D, H, W = _close_dims(x, "x", "volume_close_stats")
+    parts = int(N.lib().sa_volume_close_stat_parts(D, H, W))
+    partial = torch.empty((max(B * C * parts, 0) * 2,), device=x.device, dtype=torch.float64)
+    N.call("sa_volume_close_stats", x.data_ptr(), B, C, D, H, W, partial.data_ptr(), _stream(x))
+    return instnorm_finalize(partial, B * C, parts, D * H * W, eps)
+
+
+def volume_close_backward(grad_out: torch.Tensor, x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor,
+                          gate_left: Optional[torch.Tensor] = None, gate_right: Optional[torch.Tensor] = None,
+                          slope: float = 0.01, need_x: bool = True, need_gate_left: bool = False,
+                          need_gate_right: bool = False, out: Optional[torch.Tensor] = None):
+    """Adjoint of out = gate * lrelu((x - mean) * rstd) (sa_volume_close_backward) -> (grad_x, grad_gate_left,
+    grad_gate_right), None where not asked for.  x and grad_out [B,C,D,H,W], mean / rstd [B*C]
+    (volume_close_stats), the gates [B,C,H,W] and [B,C,H,D] or None; out: where grad_x goes (neither x
+    nor grad_out).  Deterministic."""
+    who = "volume_close_backward"
+    dims = _close_dims(x, "x", who)
+    if _close_dims(grad_out, "grad_out", who) != dims:
+        raise RuntimeError(f"{who}: grad_out must have x's shape {dims}, got {tuple(grad_out.shape)}")
+    B, C, D, H, W = dims
+    for t, nm in ((mean, "mean"), (rstd, "rstd")):
+        _check(t, nm)
+        if t.numel() != B * C:
+            raise RuntimeError(f"{who}: {nm} must have B*C = {B * C} elements, got {tuple(t.shape)}")
+    gl, gr = _close_gates(gate_left, gate_right, dims, who)
+    if (need_gate_left or need_gate_right) and gl is None:
+        raise RuntimeError(f"{who}: a gate gradient needs the gate maps")
+    if not (need_x or need_gate_left or need_gate_right):
+        raise RuntimeError(f"{who}: no gradient asked for")
+    dx = None
+    if need_x:
+        dx = torch.empty_like(x) if out is None else out
+        if _close_dims(dx, "out", who) != dims:
+            raise RuntimeError(f"{who}: out must have x's shape {dims}, got {tuple(dx.shape)}")
+    dgl = torch.empty_like(gate_left) if need_gate_left else None
+    dgr = torch.empty_like(gate_right) if need_gate_right else None
+    work = torch.empty((max(int(N.lib().sa_volume_close_backward_work(B, C, H)), 0),), device=x.device,
+                       dtype=torch.float64)
+    N.call("sa_volume_close_backward", x.data_ptr(), grad_out.data_ptr(), B, C, D, H, W, mean.data_ptr(),
+           rstd.data_ptr(), gl, gr, float(slope), work.data_ptr(), _ptr(dx), _ptr(dgl), _ptr(dgr), _stream(x))
+    return dx, dgl, dgr
+
+
 def _lookup_bytes(npix: int, nvol: int, num_levels: int, radius: int, cout: int) -> float:
     """Algorithmic bytes of one fused lookup: per pixel the coordinate, per volume the 2r + 2 cells
     of each level's window and the cout output planes."""
