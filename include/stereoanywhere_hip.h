@@ -464,7 +464,7 @@ int sa_conv3d(const float *in, int B, int Cin, int Di, int Hi, int Wi, int strid
  *   sa_conv3d_pointwise_upcat: out = Wa . Ta(a) + up(p), a [B,Ca,D,H,W], p [B,Cout,Dp,Hp,Wp]
  *     upsampled with align_corners=True (Dp-1 <= (D-1)/2 per axis), weight [Ca][Cout],
  *     plus InstanceNorm partials as for sa_conv3d (parts = sa_conv3d_upcat_stat_parts(D, H, W)).
- *     Built for (8 -> 8, identity a) and (16 -> 16, transformed a). */
+ *     Built for (8 -> 8, identity a) and (16 -> 16, transformed or identity a). */
 long sa_conv3d_upcat_stat_parts(int D, int H, int W);
 int sa_conv3d_pointwise(const float *in, int B, int Cin, int D, int H, int W, const float *mean,
                         const float *rstd, int act, float slope, const float *gate_l,
@@ -946,6 +946,39 @@ int sa_volume_close_backward(const float *x, const float *grad_out, int B, int C
                              const float *mean, const float *rstd, const float *gate_l, const float *gate_r,
                              float slope, double *work, float *grad_x, float *grad_gate_l, float *grad_gate_r,
                              void *stream);
+
+/* Backward of the hourglass's up-cat joins (upcat_backward.hip): the adjoint of out = Wa . a + up(Wu . u)
+ * as sa_conv3d_pointwise + sa_conv3d_pointwise_upcat evaluate it (hourglass.py:319-321, 326-328).  With
+ * g = dL/dout [B,Cout,D,H,W]:
+ *   dp = up^T(g)                          sa_trilinear_up_adjoint
+ *   da = Wa^T . g,   dWa = sum a g        sa_conv3d_pointwise_backward(a, g, w_a, ...)
+ *   du = Wu^T . dp,  dWu = sum u dp       sa_conv3d_pointwise_backward(u, dp, w_u, ...)
+ * Volumes are contiguous fp32.  Additive: no ABI version change; the launches are timed under SA_K_MISC.
+ * Deterministic: no atomics, every sum in an order fixed by indices.  Every refusal is made before any
+ * HIP call.
+ *
+ * sa_trilinear_up_adjoint: dp [B,C,Dp,Hp,Wp] = the transpose of upsample_trilinear3d(align_corners=True)
+ *   applied to g [B,C,D,H,W], a gather: a low-resolution cell sums its taps per column with d ascending
+ *   and h ascending within, then the columns ascending.  Taps and weights are the forward's own fp32
+ *   expressions (s = (float)(n_in - 1) / (float)(n_out - 1), i = (int)(s * (float)dst), frac = s * dst - i,
+ *   the +1 corner clamped onto i at the last cell); a cell's destination range is found by bisection on
+ *   that expression and no tap count is assumed.  Refused: null pointers, non-positive sizes, D, H or
+ *   W < 2, a low branch above half size (2 (n - 1) > N - 1 on an axis), D*H*W >= 2^31, dp overlapping g. */
+int sa_trilinear_up_adjoint(const float *g, int B, int C, int D, int H, int W, int Dp, int Hp, int Wp, float *dp,
+                            void *stream);
+/* sa_conv3d_pointwise_backward: one pass over x [B,Cx,n] and g [B,Cg,n] with w [Cx][Cg]:
+ *     dx[b,cx,i] = sum_cg w[cx][cg] g[b,cg,i]        dw[cx][cg] = sum_{b,i} x[b,cx,i] g[b,cg,i]
+ *   dx or dw may be NULL (not both): that work, its loads and its stores are skipped.  A lane adds at most
+ *   32 products in fp32 before they go into float64; a block (16384 cells of one sample, 4 waves) leaves
+ *   its waves' float64 partials in work, a fold launch (one wave per dw element) adds them in index order.
+ *   work: the caller's scratch of sa_conv3d_pointwise_backward_work(Cx, Cg, B, n) =
+ *   B ceil(n / 16384) 4 (Cx Cg / S) doubles, S = 1, 4, 2, 4 for the built pairs below (-1 for another pair
+ *   or a non-positive size), every one written before it is read; needed with dw only.
+ *   Built for (Cx, Cg) = (8, 8), (16, 16), (16, 8) and (32, 16).  Refused: null pointers, non-positive
+ *   sizes, n >= 2^31, no output, another channel pair, dx or dw overlapping x, g or w. */
+long sa_conv3d_pointwise_backward_work(int Cx, int Cg, int B, long n);
+int sa_conv3d_pointwise_backward(const float *x, const float *g, const float *w, int Cx, int Cg, int B, long n,
+                                 double *work, float *dx, float *dw, void *stream);
 
 /* Live per-kernel timing for bench.py: when enabled, every launch of kernel `id`
  * is bracketed by hipEvents on the launch stream; sa_timing_read synchronises the

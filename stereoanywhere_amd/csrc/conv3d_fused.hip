@@ -1057,6 +1057,7 @@ extern "C" int sa_conv3d_pointwise_upcat(const float *a, int Ca, const float *a_
   }
   SA_PW(8, 8, false)
   SA_PW(16, 16, true)
+  SA_PW(16, 16, false)
 #undef SA_PW
   sa::set_error("sa_conv3d_pointwise_upcat: no kernel built for %d -> %d (a transform %d)", Ca, Cout, ax);
   return SA_E_ARG;

@@ -34,6 +34,10 @@ DoubleFeatureAtt gate), on a volume a torch conv produced: differentiable with r
 both gate maps, saving the volume, the maps and the statistics (csrc/volume_close.hip);
 ``hourglass_forward`` is the reference's ``Hourglass.forward`` built on it.
 
+``upcat_conv`` is a join of that hourglass, the 1x1x1 conv over ``cat`` of a volume and a trilinearly
+up-sampled coarser one, as ``Wa . skip + up(Wu . low)``: differentiable with respect to both volumes and the
+weight, saving exactly those three (csrc/upcat_backward.hip); ``hourglass_forward(joins="hip")`` uses it.
+
 Floating inputs that are not fp32 (fp16 / bf16 activations under ``torch.autocast``) are cast with
 ``.float()``: a torch op, so the gradient arrives at the caller's tensor in its own dtype.  There is
 no CPU path.
@@ -498,20 +502,125 @@ def volume_close(x, gate_left=None, gate_right=None, negative_slope: float = 0.0
     return _VolumeCloseFn.apply(x, gate_left, gate_right, float(negative_slope), float(eps))
 
 
-def _close_layer(conv_block, x, gate=None):
-    """One BasicConv (its own nn.Conv3d on torch, then the fused close) -> its output volume."""
-    return volume_close(conv_block.conv(x), *(gate or (None, None)),
+# ------------------------------------------------------------------------------- up-cat conv
+# (skip channels, low-branch channels, output channels) of the hourglass's two joins (hourglass.py:319-321,
+# 326-328): what sa_conv3d_pointwise, sa_conv3d_pointwise_upcat and sa_conv3d_pointwise_backward are built for
+UPCAT_TRIPLES = ((8, 16, 8), (16, 32, 16))
+# ((Ca, Cu, Cout), low_first) of the published 8-channel hourglass: final_agg[0] over cat(orig, up) and
+# agg_layers[1][0] over cat(up, down0); hourglass_forward(joins="hip") takes upcat_conv for these
+HOURGLASS_JOINS = (((8, 16, 8), False), ((16, 32, 16), True))
+
+
+def _upcat_problem(skip, low, weight):
+    """None when ``upcat_conv`` is built for these tensors, else what is wrong with them."""
+    if skip.dim() != 5 or low.dim() != 5 or weight.dim() != 5:
+        return f"skip, low and weight must be 5-D, got {tuple(skip.shape)}, {tuple(low.shape)}, {tuple(weight.shape)}"
+    (B, ca, D, H, W), (Bl, cu, Dp, Hp, Wp) = skip.shape, low.shape
+    cout = weight.shape[0]
+    if tuple(weight.shape[1:]) != (ca + cu, 1, 1, 1) or Bl != B:
+        return (f"weight must be [Cout, Ca + Cu = {ca + cu}, 1, 1, 1] and the batches equal, got weight "
+                f"{tuple(weight.shape)}, skip {tuple(skip.shape)}, low {tuple(low.shape)}")
+    if (ca, cu, cout) not in UPCAT_TRIPLES:
+        return f"built for (Ca, Cu, Cout) in {UPCAT_TRIPLES}, got {(ca, cu, cout)}"
+    if min(D, H, W) < 2:
+        return f"D, H and W must be at least 2, got {(D, H, W)}"
+    if min(Dp, Hp, Wp) < 1 or any(2 * (n - 1) > N - 1 for n, N in zip((Dp, Hp, Wp), (D, H, W))):
+        return (f"the low branch must be at most half size (2 (n - 1) <= N - 1 per axis), got {(Dp, Hp, Wp)} "
+                f"under {(D, H, W)}")
+    if D * H * W >= 2 ** 31:
+        return f"D*H*W must be below 2^31, got {(D, H, W)}"
+    return None
+
+
+def _upcat_weights(weight, ca: int, low_first: bool):
+    """The module's [Cout, Ca+Cu, 1, 1, 1] weight -> (w_a [Ca][Cout], w_u [Cu][Cout]), contiguous."""
+    w = weight.reshape(weight.shape[0], -1)
+    cu = w.shape[1] - ca
+    w_a, w_u = (w[:, cu:], w[:, :cu]) if low_first else (w[:, :ca], w[:, ca:])
+    return w_a.t().contiguous(), w_u.t().contiguous()
+
+
+class _UpcatConvFn(torch.autograd.Function):
+    """ops.conv3d_pointwise_upcat (Wa . skip + up(Wu . low), two launches) with ops.trilinear_up_adjoint and
+    ops.conv3d_pointwise_backward as the adjoint.  Saves skip, low and the weight: the up-sampled and the
+    concatenated volume exist in neither direction."""
+
+    @staticmethod
+    def forward(ctx, skip, low, weight, low_first):
+        ctx.save_for_backward(skip, low, weight)
+        ctx.low_first = low_first
+        w_a, w_u = _upcat_weights(weight, skip.shape[1], low_first)
+        return ops.conv3d_pointwise_upcat(ops.VolAct(skip), ops.VolAct(low), w_a, w_u, weight.shape[0],
+                                          stats=False).raw
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        skip, low, weight = ctx.saved_tensors
+        need_skip, need_low, need_w = ctx.needs_input_grad[:3]
+        if not (need_skip or need_low or need_w):
+            return None, None, None, None
+        grad = grad.float().contiguous()
+        w_a, w_u = _upcat_weights(weight, skip.shape[1], ctx.low_first)
+        d_skip = d_low = d_weight = dw_a = dw_u = None
+        if need_skip or need_w:
+            d_skip, dw_a = ops.conv3d_pointwise_backward(skip, grad, w_a, need_skip, need_w)
+        if need_low or need_w:
+            dp = ops.trilinear_up_adjoint(grad, low.shape[2:])
+            d_low, dw_u = ops.conv3d_pointwise_backward(low, dp, w_u, need_low, need_w)
+        if need_w:
+            d_weight = torch.cat((dw_u, dw_a) if ctx.low_first else (dw_a, dw_u), 0).t().reshape(weight.shape)
+        return d_skip, d_low, d_weight, None
+
+
+def upcat_conv(skip, low, weight, low_first: bool) -> torch.Tensor:
+    """``conv3d(cat((up(low), skip) if low_first else (skip, up(low)), 1), weight)`` with
+    ``up = interpolate(size=skip.shape[2:], mode="trilinear", align_corners=True)``: a join of the hourglass
+    (hourglass.py:319-321, 326-328) as ``Wa . skip + up(Wu . low)``, the low branch projected onto the output
+    channels before it is up-sampled, so neither the up-sampled nor the concatenated volume is written or
+    kept (csrc/conv3d_fused.hip forward, csrc/upcat_backward.hip backward).  skip [B,Ca,D,H,W], low
+    [B,Cu,Dp,Hp,Wp] at most half size per axis, weight the module's own [Cout, Ca+Cu, 1, 1, 1] (no bias);
+    built for (Ca, Cu, Cout) in ``UPCAT_TRIPLES``.  Differentiable with respect to all three; saves exactly
+    them; each gradient is computed only where it is needed."""
+    for t, name in ((skip, "skip"), (low, "low"), (weight, "weight")):
+        _on_gpu(t, name)
+    problem = _upcat_problem(skip, low, weight)
+    if problem is not None:
+        raise ValueError(f"upcat_conv: {problem}")
+    return _UpcatConvFn.apply(skip.float().contiguous(), low.float().contiguous(), weight.float().contiguous(),
+                              bool(low_first))
+
+
+def _join(conv, skip, low, low_first: bool, joins: str):
+    """The first conv of a join's Sequential on cat(skip, up(low)): ``upcat_conv`` with joins="hip" where the
+    join is one of the published hourglass's two (``HOURGLASS_JOINS``) on a plain 1x1x1 conv and the sizes
+    are built, else torch's interpolate + cat + conv: a narrower or wider hourglass runs wholly on torch."""
+    triple = (skip.shape[1], low.shape[1], getattr(conv, "out_channels", None))
+    if (joins == "hip" and (triple, low_first) in HOURGLASS_JOINS and isinstance(conv, torch.nn.Conv3d)
+            and conv.bias is None and conv.groups == 1
+            and tuple(conv.stride) == (1, 1, 1) and tuple(conv.padding) == (0, 0, 0)
+            and _upcat_problem(skip, low, conv.weight) is None):
+        return upcat_conv(skip, low, conv.weight, low_first)
+    up = torch.nn.functional.interpolate(low, size=skip.shape[2:], mode="trilinear", align_corners=True)
+    return conv(torch.cat((up, skip) if low_first else (skip, up), 1))
+
+
+def _close_layer(conv_block, x, gate=None, conv_out=None):
+    """One BasicConv (its own nn.Conv3d on torch unless its output ``conv_out`` is given, then the fused
+    close) -> its output volume."""
+    return volume_close(conv_block.conv(x) if conv_out is None else conv_out, *(gate or (None, None)),
                         negative_slope=getattr(conv_block.act_fn, "negative_slope", 0.01),
                         eps=getattr(conv_block.norm_fn, "eps", 1e-5))
 
 
-def _close_gated(layers, att, x, feat_left, feat_right):
+def _close_gated(layers, att, x, feat_left, feat_right, first=None):
     """A Sequential of BasicConvs followed by a DoubleFeatureAtt: the gate goes into the last close when
     its maps are at the volume's resolution, else that close runs gate-less and the module's own
-    interpolate-and-multiply follows."""
-    for layer in list(layers)[:-1]:
-        x = _close_layer(layer, x)
-    y = layers[-1].conv(x)
+    interpolate-and-multiply follows.  ``first``: the first layer's conv output where a join made it
+    (x is unused then)."""
+    for k, layer in enumerate(list(layers)[:-1]):
+        x = _close_layer(layer, x, conv_out=first if k == 0 else None)
+    y = first if first is not None and len(layers) == 1 else layers[-1].conv(x)
     gl = torch.sigmoid(att.feat_att_left(feat_left))
     gr = torch.sigmoid(att.feat_att_right(feat_right))
     D, H, W = y.shape[2:]
@@ -524,7 +633,7 @@ def _close_gated(layers, att, x, feat_left, feat_right):
     return g * volume_close(y, **last)
 
 
-def hourglass_forward(hg, x, features_left, features_right, layout: str = "reference"):
+def hourglass_forward(hg, x, features_left, features_right, layout: str = "reference", joins: str = "torch"):
     """The live part of the reference's ``Hourglass.forward`` (hourglass.py:61-91) for fine-tuning: the
     module's own ``nn.Conv3d``s on torch / MIOpen, every InstanceNorm3d + LeakyReLU (+ the following
     DoubleFeatureAtt) as one ``volume_close``.  The deepest down layer and the first up-path step feed
@@ -534,10 +643,13 @@ def hourglass_forward(hg, x, features_left, features_right, layout: str = "refer
     ``final_agg``, ``feature_atts``, ``feature_atts_up``, ``final_feature_atts_up`` and
     ``number_of_scales`` are used).  layout="reference" takes and returns [B,C,H,W1,W2] with the
     reference's permutes (``types.MethodType(hourglass_forward, hg)`` replaces its forward);
-    layout="volume" works on [B,C,W2,H,W1].  Trilinear up-sampling and ``cat`` stay on torch."""
+    layout="volume" works on [B,C,W2,H,W1].  joins="torch": the two joins (trilinear up-sampling, ``cat``
+    and the 1x1x1 conv) stay on torch; joins="hip": each runs as one ``upcat_conv`` where that is built
+    for its channels and sizes (the published 8-channel hourglass), else on torch."""
     if layout not in ("reference", "volume"):
         raise ValueError(f"hourglass_forward: layout must be 'reference' or 'volume', got {layout!r}")
-    interpolate = torch.nn.functional.interpolate
+    if joins not in ("torch", "hip"):
+        raise ValueError(f"hourglass_forward: joins must be 'torch' or 'hip', got {joins!r}")
     ns = hg.number_of_scales
     if layout == "reference":
         x = x.permute(0, 1, 3, 2, 4).permute(0, 1, 4, 3, 2)
@@ -547,12 +659,11 @@ def hourglass_forward(hg, x, features_left, features_right, layout: str = "refer
         x = _close_gated(hg.down_layers[i], hg.feature_atts[i], x, features_left[i + 1], features_right[i + 1])
         downs.append(x)
     i = ns - 3
-    up = interpolate(downs[ns - 2 - i], size=downs[ns - 3 - i].shape[2:], mode="trilinear", align_corners=True)
-    x = _close_gated(hg.agg_layers[i], hg.feature_atts_up[i], torch.cat((up, downs[ns - 3 - i]), 1),
-                     features_left[ns - 2 - i], features_right[ns - 2 - i])
-    up = interpolate(x, size=orig.shape[2:], mode="trilinear", align_corners=True)
-    x = _close_gated(hg.final_agg, hg.final_feature_atts_up, torch.cat((orig, up), 1), features_left[0],
-                     features_right[0])
+    y = _join(hg.agg_layers[i][0].conv, downs[ns - 3 - i], downs[ns - 2 - i], True, joins)
+    x = _close_gated(hg.agg_layers[i], hg.feature_atts_up[i], None, features_left[ns - 2 - i],
+                     features_right[ns - 2 - i], first=y)
+    y = _join(hg.final_agg[0].conv, orig, x, False, joins)
+    x = _close_gated(hg.final_agg, hg.final_feature_atts_up, None, features_left[0], features_right[0], first=y)
     if layout == "reference":
         x = x.permute(0, 1, 4, 3, 2).permute(0, 1, 3, 2, 4)
     return x

@@ -500,6 +500,67 @@ def volume_close_backward(grad_out: torch.Tensor, x: torch.Tensor, mean: torch.T
     return dx, dgl, dgr
 
 
+# ------------------------------------------------------------------------------- up-cat conv backward
+def trilinear_up_adjoint(grad: torch.Tensor, low_size, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The transpose of ``F.interpolate(p, size=grad.shape[2:], mode="trilinear", align_corners=True)``
+    applied to grad [B,C,D,H,W] -> dp [B,C,*low_size] (sa_trilinear_up_adjoint): a gather with the taps and
+    weights of sa_conv3d_pointwise_upcat's own fp32 expressions.  low_size at most half size per axis
+    (2 (n - 1) <= N - 1); out: where dp goes.  Deterministic."""
+    who = "trilinear_up_adjoint"
+    B, C, D, H, W = _close_dims(grad, "grad", who)
+    Dp, Hp, Wp = (int(v) for v in low_size)
+    if out is None:
+        out = torch.empty((B, C, Dp, Hp, Wp), device=grad.device, dtype=torch.float32)
+    elif _close_dims(out, "out", who) != (B, C, Dp, Hp, Wp):
+        raise RuntimeError(f"{who}: out must be {(B, C, Dp, Hp, Wp)}, got {tuple(out.shape)}")
+    N.call("sa_trilinear_up_adjoint", grad.data_ptr(), B, C, D, H, W, Dp, Hp, Wp, out.data_ptr(), _stream(grad))
+    return out
+
+
+def conv3d_pointwise_backward_work(cx: int, cg: int, B: int, n: int) -> int:
+    """Doubles of scratch sa_conv3d_pointwise_backward needs for dw; -1 where no kernel is built."""
+    return int(N.lib().sa_conv3d_pointwise_backward_work(cx, cg, B, n))
+
+
+def conv3d_pointwise_backward(x: torch.Tensor, grad: torch.Tensor, w_t: torch.Tensor, need_x: bool = True,
+                              need_w: bool = True, out: Optional[torch.Tensor] = None,
+                              work: Optional[torch.Tensor] = None):
+    """Adjoint of the 1x1x1 conv y = W . x with w_t [Cx][Cg] (sa_conv3d_pointwise_backward), one pass over
+    x [B,Cx,D,H,W] and grad [B,Cg,D,H,W] -> (dx = W . grad like x, dw [Cx][Cg] = sum x grad), None where not
+    asked for (that work is skipped).  out: where dx goes; work: the float64 scratch
+    (conv3d_pointwise_backward_work doubles).  Built for (Cx, Cg) = (8, 8), (16, 16), (16, 8), (32, 16).
+    Deterministic."""
+    who = "conv3d_pointwise_backward"
+    B, Cx, D, H, W = _close_dims(x, "x", who)
+    gd = _close_dims(grad, "grad", who)
+    if (gd[0],) + gd[2:] != (B, D, H, W):
+        raise RuntimeError(f"{who}: grad must be [B,Cg,D,H,W] over x's cells {(B, D, H, W)}, got {gd}")
+    Cg = gd[1]
+    _check(w_t, "w_t")
+    if tuple(w_t.shape) != (Cx, Cg):
+        raise RuntimeError(f"{who}: w_t must be [Cx][Cg] = {(Cx, Cg)}, got {tuple(w_t.shape)}")
+    if not (need_x or need_w):
+        raise RuntimeError(f"{who}: no gradient asked for")
+    n = D * H * W
+    if conv3d_pointwise_backward_work(Cx, Cg, B, n) < 0:
+        raise RuntimeError(f"{who}: no kernel built for {Cx} x {Cg} (built: 8 x 8, 16 x 16, 16 x 8, 32 x 16)")
+    dx = dw = None
+    if need_x:
+        dx = torch.empty_like(x) if out is None else out
+        if _close_dims(dx, "out", who) != (B, Cx, D, H, W):
+            raise RuntimeError(f"{who}: out must have x's shape, got {tuple(dx.shape)}")
+    if need_w:
+        count = conv3d_pointwise_backward_work(Cx, Cg, B, n)
+        if work is None:
+            work = torch.empty((max(count, 0),), device=x.device, dtype=torch.float64)
+        elif work.dtype != torch.float64 or work.device != x.device or not work.is_contiguous() or work.numel() < count:
+            raise RuntimeError(f"{who}: work must hold {count} contiguous float64 on {x.device}")
+        dw = torch.empty((Cx, Cg), device=x.device, dtype=torch.float32)
+    N.call("sa_conv3d_pointwise_backward", x.data_ptr(), grad.data_ptr(), w_t.data_ptr(), Cx, Cg, B, n,
+           _ptr(work) if need_w else None, _ptr(dx), _ptr(dw), _stream(x))
+    return dx, dw
+
+
 def _lookup_bytes(npix: int, nvol: int, num_levels: int, radius: int, cout: int) -> float:
     """Algorithmic bytes of one fused lookup: per pixel the coordinate, per volume the 2r + 2 cells
     of each level's window and the cout output planes."""
@@ -1352,9 +1413,10 @@ def conv3d_pointwise(x: "VolAct", w_t: torch.Tensor, cout: int, slope: float = 0
 
 
 def conv3d_pointwise_upcat(a: "VolAct", u: "VolAct", w_a: torch.Tensor, w_u: torch.Tensor, cout: int,
-                           slope: float = 0.01) -> "VolAct":
+                           slope: float = 0.01, stats: bool = True) -> "VolAct":
     """1x1x1 conv over cat(T(a), trilinear_up(T(u))) -> VolAct(out, IN stats, act=True), as
-    Wa.T(a) + up(Wu.T(u)) (two launches); w_a [Ca][Cout], w_u [Cu][Cout]."""
+    Wa.T(a) + up(Wu.T(u)) (two launches); w_a [Ca][Cout], w_u [Cu][Cout].  stats=False (the dense
+    form only): the kernel's statistics partials are dropped and the plain VolAct(out) returned."""
     if isinstance(a, OneHotVolume):
         p = conv3d_pointwise(u, w_u, cout, slope)
         B, _, D, H, W = a.shape
@@ -1375,6 +1437,8 @@ def conv3d_pointwise_upcat(a: "VolAct", u: "VolAct", w_a: torch.Tensor, w_u: tor
     partial = torch.empty((B * cout * parts * 2,), device=out.device, dtype=torch.float64)
     N.call("sa_conv3d_pointwise_upcat", a.raw.data_ptr(), Ca, *a.args(), p.data_ptr(), Dp, Hp, Wp, B, D,
            H, W, slope, w_a.data_ptr(), cout, out.data_ptr(), partial.data_ptr(), _stream(out))
+    if not stats:
+        return VolAct(out)
     return VolAct(out, instnorm_finalize(partial, B * cout, parts, D * H * W), act=True)
 
 
