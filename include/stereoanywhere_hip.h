@@ -515,6 +515,14 @@ int sa_conv3d_mf(const float *in, int B, int Cin, int D, int H, int W, const voi
                  double *stats_partial, void *stream);
 void sa_conv3d_mf_set_planes(int planes);
 int sa_conv3d_mf_get_planes(void);
+/* sa_conv3d_mf with a per-sample output factor: out = conv(T(in)) * out_scale[b], out_scale [B] powers of
+ * two (required), folded into the epilogue's constant 2^-12.  With in_mean = 0, in_rstd[b, ci] = s_b, slope = 1
+ * and out_scale[b] = 1 / s_b (sa_sample_scale's two outputs) this is the conv of an input of any range;
+ * in_rstd = 1, out_scale = 1 is the identity transform.  sa_conv3d_mf itself passes no factor and keeps its
+ * bits.  Additive: no ABI version change. */
+int sa_conv3d_mf_scaled(const float *in, int B, int Cin, int D, int H, int W, const void *table, int Cout,
+                        const float *in_mean, const float *in_rstd, float slope, const float *out_scale, float *out,
+                        double *stats_partial, void *stream);
 /* The hourglass's stride-2 16 -> 32 conv (down_layers[1][0], hourglass.py:27-33, submodule.py:25-53)
  * on the same split-f16 MFMA: in [B][16][D][H][W] with the producer's InstanceNorm (mean / rstd
  * [B*16]) + LeakyReLU(slope) and the optional feature-attention gate (sa_conv3d's gate_l / gate_r)
@@ -979,6 +987,38 @@ int sa_trilinear_up_adjoint(const float *g, int B, int C, int D, int H, int W, i
 long sa_conv3d_pointwise_backward_work(int Cx, int Cg, int B, long n);
 int sa_conv3d_pointwise_backward(const float *x, const float *g, const float *w, int Cx, int Cg, int B, long n,
                                  double *work, float *dx, float *dw, void *stream);
+
+/* Backward of the stride-1 3x3x3 hourglass convs with Cin = Cout = C in {8, 16, 32} (conv3d_backward.hip;
+ * sa_conv3d_mf is their forward).  With g = dL/dout [B,C,D,H,W], contiguous fp32:
+ *   dx = conv3d(g, flip(w), channel roles swapped)         sa_conv3d_mf_scaled on a second table
+ *   dw[ci][tap][co] = sum_b sum_p x[b,ci,p+tap-1] g[b,co,p]  sa_conv3d_k3_backward_weight
+ * Additive: no ABI version change; the launches are timed under SA_K_MISC.  Every refusal is made before any
+ * HIP call.
+ *
+ * sa_sample_scale: per sample b of t [B][n] one power of two s_b = 2^k with max |t_b| s_b in [2^13, 2^14)
+ *   (k = 14 - e for a maximum in [2^(e-1), 2^e), clamped to |k| <= 100 so that s_b, 1 / s_b and 2^-12 / s_b
+ *   stay normal fp32); s_b = 1 for an all-zero sample and for one that holds an inf or a NaN, which then
+ *   propagate.  One launch (after a memset of state), no host sync: the sample's blocks fold max |t| as
+ *   unsigned bits, the last of them writes scale[b * rep .. b * rep + rep - 1] = s_b (rep = C gives
+ *   sa_conv3d_mf_scaled's in_rstd) and inv[b] = 1 / s_b.  state: 2 B unsigned of caller scratch.  The
+ *   maximum does not depend on the order it is taken in, so the result is deterministic.  Refused: null
+ *   pointers, B outside 1 .. 65535, n or rep < 1. */
+int sa_sample_scale(const float *t, int B, long n, int rep, void *state, float *scale, float *inv, void *stream);
+/* sa_conv3d_k3_backward_weight: dw [C][27][C] (ops.conv3d's [Cin][27][Cout]) of a stride-1, pad-1 conv from
+ *   x and g [B,C,D,H,W] on v_mfma_f32_16x16x32_f16 with split operands (hi hi + hi lo + lo hi), K = cells.
+ *   x_scale / g_scale [B]: the samples' powers of two (sa_sample_scale's `scale` at rep 1) the operands are
+ *   multiplied by before the split; NULL = 1, for an operand the caller knows to be bounded, |v| < 2^15 (a
+ *   larger one gives inf hi halves, so non-finite dw).  An fp32 accumulator takes at most R = 1024 products
+ *   before it is added into float64; a block (one sample, a 4 x 64 or 4 x 32 tile of (h, w), a range of
+ *   planes) multiplies its float64 sums by the exact inverse scales and leaves them in work, a fold launch
+ *   (one wave per dw element) adds the blocks' partials in index order.  No atomics.
+ *   work: sa_conv3d_k3_backward_weight_work(C, B, D, H, W) doubles of caller scratch (-1 for another C or a
+ *   non-positive size), every one written before it is read; the count follows sa_conv3d_mf_set_planes.
+ *   Refused: null pointers (x, g, work, dw), non-positive sizes, another C, D*H*W >= 2^30, dw or work
+ *   overlapping an input or each other. */
+long sa_conv3d_k3_backward_weight_work(int C, int B, int D, int H, int W);
+int sa_conv3d_k3_backward_weight(const float *x, const float *g, int C, int B, int D, int H, int W,
+                                 const float *x_scale, const float *g_scale, double *work, float *dw, void *stream);
 
 /* Live per-kernel timing for bench.py: when enabled, every launch of kernel `id`
  * is bracketed by hipEvents on the launch stream; sa_timing_read synchronises the

@@ -184,15 +184,19 @@ class Hourglass(nn.Module):
         self.final_feature_atts_up = DoubleFeatureAtt(out_channels, fc[0])
         self.number_of_scales = ns
 
-    def forward(self, x, features_left, features_right, fused=None, closes=None, joins=None):
+    def forward(self, x, features_left, features_right, fused=None, closes=None, joins=None, convs=None):
         """``fused``: pre-arranged weights (StereoAnywhere._weights()["hg"]) to run the whole
         hourglass plus both classifiers through the fused HIP convolutions (see
         _forward_fused); returns (vol_disp, vol_conf) then.  Without it: torch/MIOpen.
         ``closes="hip"`` (fine-tuning): the torch convs with every InstanceNorm3d + LeakyReLU
         (+ DoubleFeatureAtt) as one differentiable HIP close (diffops.hourglass_forward).
         ``joins="hip"`` (with ``closes="hip"``): the two up-sample + cat + 1x1x1 conv joins as
-        diffops.upcat_conv where it is built for their channels and sizes; None: on torch."""
+        diffops.upcat_conv where it is built for their channels and sizes; None: on torch.
+        ``convs="hip"`` (with ``closes="hip"``): the stride-1 3x3x3 convs that follow a close as
+        diffops.conv3d_k3 where it is built for their channels and sizes; None: on torch."""
         ns = self.number_of_scales
+        if convs not in (None, "hip"):
+            raise ValueError(f"convs must be None or 'hip', got {convs!r}")
         if joins not in (None, "hip"):
             raise ValueError(f"joins must be None or 'hip', got {joins!r}")
         if fused is not None:
@@ -202,9 +206,12 @@ class Hourglass(nn.Module):
                 raise ValueError(f"closes must be None or 'hip', got {closes!r}")
             from . import diffops
             return diffops.hourglass_forward(self, x, features_left, features_right, layout="volume",
-                                             joins="torch" if joins is None else joins)
+                                             joins="torch" if joins is None else joins,
+                                             convs="torch" if convs is None else convs)
         if joins is not None:
             raise ValueError("joins='hip' goes with closes='hip'")
+        if convs is not None:
+            raise ValueError("convs='hip' goes with closes='hip'")
         orig = x
         downs = []
         # only downsampled_features[0 .. ns-3] feed the live up-path step (class docstring):

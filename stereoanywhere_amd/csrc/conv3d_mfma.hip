@@ -10,7 +10,9 @@
 // exact, so the sum carries ~2^-22 relative error per term - the fp32 kernels' accuracy.  No
 // range guard is needed: an InstanceNorm'ed value satisfies sum(v^2) = n var / (var + eps) <= n
 // over its n = D*H*W voxels, so |v| <= sqrt(n) < 2^15 for n < 2^30 (the host requires it), and
-// LeakyReLU only shrinks it; weights with |w| * 2^12 >= 2^15 are refused by ops.py.
+// LeakyReLU only shrinks it; weights with |w| * 2^12 >= 2^15 are refused by ops.py.  An input without
+// that bound (a gradient volume: conv3d_backward.hip) comes through sa_conv3d_mf_scaled with a
+// per-sample power of two as its rstd (mean 0, slope 1) and the inverse in the epilogue's factor.
 //
 // GEMM mapping (one wave, one MFMA): M = 16 consecutive output columns w, N = 16 output
 // channels x planes, K = 32 = 4 groups of 8 input channels at one input plane:
@@ -113,6 +115,7 @@ __attribute__((amdgpu_waves_per_eu(MfCfg<CIN, COUT>::WPE, MfCfg<CIN, COUT>::WPE)
                                                                 const f16x8 *__restrict__ wtab,
                                                                 const float *__restrict__ mean,
                                                                 const float *__restrict__ rstd, float slope,
+                                                                const float *__restrict__ out_scale,
                                                                 float *__restrict__ out, double *__restrict__ partial,
                                                                 int tilesW, int tilesH, int tilesD, int DR) {
   using C = MfCfg<CIN, COUT>;
@@ -129,6 +132,11 @@ __attribute__((amdgpu_waves_per_eu(MfCfg<CIN, COUT>::WPE, MfCfg<CIN, COUT>::WPE)
   wtab += ch * C::TAB;
   const int w0 = bx * C::TW, h0 = by * C::TH, d0 = dz * DR, d1 = min(d0 + DR, D);
   const long HW = (long)H * W;
+  // the epilogue's factor: 1 / kSplitScale, times the sample's power of two where the caller scaled the input
+  // (kept in a scalar register: the product is VALU work, and a vector register more would cost the kernels theirs)
+  const float unscale = __builtin_bit_cast(
+      float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(
+                 int, out_scale ? out_scale[b] * (1.0f / sa::kSplitScale) : 1.0f / sa::kSplitScale)));
 
   // T(x) = lrelu(x * rstd - mean * rstd); the whole ring starts zeroed: entries outside H x W
   // (the zero padding) are never written again
@@ -286,7 +294,7 @@ __attribute__((amdgpu_waves_per_eu(MfCfg<CIN, COUT>::WPE, MfCfg<CIN, COUT>::WPE)
         const int w = wl + 16 * u;
         float v[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = acc[u][j] * (1.0f / sa::kSplitScale);
+        for (int j = 0; j < 4; ++j) v[j] = acc[u][j] * unscale;
         if (vec && w + 3 < W) {
           *reinterpret_cast<float4 *>(o + w) = make_float4(v[0], v[1], v[2], v[3]);
 #pragma unroll
@@ -408,9 +416,11 @@ extern "C" long sa_conv3d_mf_stat_parts(int B, int Cin, int Cout, int D, int H, 
   return (long)g.tilesW * g.tilesH * g.tilesD;
 }
 
-extern "C" int sa_conv3d_mf(const float *in, int B, int Cin, int D, int H, int W, const void *table, int Cout,
-                            const float *in_mean, const float *in_rstd, float slope, float *out,
-                            double *stats_partial, void *stream) {
+namespace {
+
+int mf_launch(const float *in, int B, int Cin, int D, int H, int W, const void *table, int Cout, const float *in_mean,
+              const float *in_rstd, float slope, const float *out_scale, float *out, double *stats_partial,
+              void *stream) {
   SA_REQUIRE(in && table && out && in_mean && in_rstd, "sa_conv3d_mf: null pointer");
   SA_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, "sa_conv3d_mf: empty shape");
   SA_REQUIRE(mf_shape(Cin, Cout), "sa_conv3d_mf: built for 8 -> 8, 16 -> 16 and 32 -> 32 (got %d -> %d)", Cin, Cout);
@@ -427,10 +437,25 @@ extern "C" int sa_conv3d_mf(const float *in, int B, int Cin, int D, int H, int W
   const f16x8 *t = reinterpret_cast<const f16x8 *>(table);
 #define SA_MF(CI)                                                                                             \
   conv3d_mf_kernel<CI, CI><<<(unsigned)blocks, MfCfg<CI, CI>::NTHR, 0, s>>>(                                  \
-      in, D, H, W, t, in_mean, in_rstd, slope, out, stats_partial, g.tilesW, g.tilesH, g.tilesD, g.DR)
+      in, D, H, W, t, in_mean, in_rstd, slope, out_scale, out, stats_partial, g.tilesW, g.tilesH, g.tilesD, g.DR)
   if (Cin == 8) SA_MF(8);
   else if (Cin == 16) SA_MF(16);
   else SA_MF(32);
 #undef SA_MF
   return sa::check_launch("sa_conv3d_mf");
+}
+
+}  // namespace
+
+extern "C" int sa_conv3d_mf(const float *in, int B, int Cin, int D, int H, int W, const void *table, int Cout,
+                            const float *in_mean, const float *in_rstd, float slope, float *out,
+                            double *stats_partial, void *stream) {
+  return mf_launch(in, B, Cin, D, H, W, table, Cout, in_mean, in_rstd, slope, nullptr, out, stats_partial, stream);
+}
+
+extern "C" int sa_conv3d_mf_scaled(const float *in, int B, int Cin, int D, int H, int W, const void *table, int Cout,
+                                   const float *in_mean, const float *in_rstd, float slope, const float *out_scale,
+                                   float *out, double *stats_partial, void *stream) {
+  SA_REQUIRE(out_scale, "sa_conv3d_mf_scaled: null pointer (out_scale)");
+  return mf_launch(in, B, Cin, D, H, W, table, Cout, in_mean, in_rstd, slope, out_scale, out, stats_partial, stream);
 }

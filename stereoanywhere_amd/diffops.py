@@ -38,6 +38,11 @@ both gate maps, saving the volume, the maps and the statistics (csrc/volume_clos
 up-sampled coarser one, as ``Wa . skip + up(Wu . low)``: differentiable with respect to both volumes and the
 weight, saving exactly those three (csrc/upcat_backward.hip); ``hourglass_forward(joins="hip")`` uses it.
 
+``conv3d_k3`` is a stride-1 3x3x3 conv of that hourglass with equal channel counts (8, 16 or 32): the inference
+split-f16 MFMA kernel forward and, with the flipped kernel, for the data gradient, a HIP weight gradient
+(csrc/conv3d_backward.hip), per-sample power-of-two scales where an operand has no known range; saves exactly the
+input and the weight; ``hourglass_forward(convs="hip")`` uses it.
+
 Floating inputs that are not fp32 (fp16 / bf16 activations under ``torch.autocast``) are cast with
 ``.float()``: a torch op, so the gradient arrives at the caller's tensor in its own dtype.  There is
 no CPU path.
@@ -605,22 +610,115 @@ def _join(conv, skip, low, low_first: bool, joins: str):
     return conv(torch.cat((up, skip) if low_first else (skip, up), 1))
 
 
-def _close_layer(conv_block, x, gate=None, conv_out=None):
-    """One BasicConv (its own nn.Conv3d on torch unless its output ``conv_out`` is given, then the fused
-    close) -> its output volume."""
-    return volume_close(conv_block.conv(x) if conv_out is None else conv_out, *(gate or (None, None)),
+# ------------------------------------------------------------------------------- 3x3x3 conv
+def _k3_problem(x, weight):
+    """None when ``conv3d_k3`` is built for these tensors, else what is wrong with them."""
+    if x.dim() != 5 or weight.dim() != 5:
+        return f"x and weight must be 5-D, got {tuple(x.shape)}, {tuple(weight.shape)}"
+    B, C, D, H, W = x.shape
+    if C not in ops.CONV3D_K3_CHANNELS or tuple(weight.shape) != (C, C, 3, 3, 3):
+        return (f"built for [C, C, 3, 3, 3] weights with C in {ops.CONV3D_K3_CHANNELS} on [B, C, D, H, W], got "
+                f"weight {tuple(weight.shape)}, x {tuple(x.shape)}")
+    if min(B, D, H, W) < 1:
+        return f"empty volume {tuple(x.shape)}"
+    if D * H * W >= 2 ** 30:
+        return f"D*H*W must be below 2^30, got {(D, H, W)}"
+    if C * D * H * W * 4 >= 2 ** 31:
+        return f"a sample's volume C*D*H*W*4 must be below 2^31 bytes, got {(C, D, H, W)}"
+    return None
+
+
+class _Conv3dK3Fn(torch.autograd.Function):
+    """sa_conv3d_mf_scaled forward and, on the flipped and channel-swapped table, for dx;
+    sa_conv3d_k3_backward_weight for dw.  Saves x and the weight; both tables and every scale are rebuilt."""
+
+    @staticmethod
+    def forward(ctx, x, weight, x_bounded):
+        ctx.save_for_backward(x, weight)
+        ctx.x_bounded = x_bounded
+        C = x.shape[1]
+        table = ops.conv3d_mf_table(weight.reshape(C, C, 27).permute(1, 2, 0).contiguous())   # [ci][tap][co]
+        scales = (None, None) if x_bounded else ops.sample_scale(x, C)
+        return ops.conv3d_mf_scaled(x, table, *scales)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        x, weight = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[:2]
+        if not (need_x or need_w):
+            return None, None, None
+        grad = grad.float().contiguous()
+        B, C = x.shape[:2]
+        g_scale, g_inv = ops.sample_scale(grad, C)   # one launch, for dx and dw
+        dx = dw = None
+        if need_x:
+            # dx[ci] = sum_co conv(g[co], w[co][ci] flipped): a conv with co as its input channels
+            table = ops.conv3d_mf_table(weight.reshape(C, C, 27).flip(2).permute(0, 2, 1).contiguous())
+            dx = ops.conv3d_mf_scaled(grad, table, g_scale, g_inv)
+        if need_w:
+            x_scale = None if ctx.x_bounded else ops.sample_scale(x, 1)[0]
+            dw_t = ops.conv3d_k3_backward_weight(x, grad, x_scale, g_scale.view(B, C)[:, 0].contiguous())
+            dw = dw_t.permute(2, 0, 1).reshape(weight.shape)
+        return dx, dw, None
+
+
+def conv3d_k3(x, weight, x_bounded: bool = False, check_weight: bool = False) -> torch.Tensor:
+    """``F.conv3d(x, weight, padding=1)`` for x [B,C,D,H,W] and the module's own [C, C, 3, 3, 3] weight (stride
+    1, no bias), C in ``ops.CONV3D_K3_CHANNELS``, on the inference path's split-f16 MFMA kernel at fp32-level
+    accuracy (csrc/conv3d_mfma.hip), differentiable with respect to both (csrc/conv3d_backward.hip): dx is the
+    same kernel on the gradient with the flipped, channel-swapped weight, dw a split-f16 MFMA reduction over
+    cells folded in float64.  Saves exactly x and weight; each gradient is computed only where it is needed.
+
+    The kernel needs |value| < 2^15.  A gradient has no such bound, so it is multiplied per sample by a power
+    of two that brings its maximum into [2^13, 2^14) and the result divided by it again (exact; found on the
+    device, no host sync); x is treated the same way unless ``x_bounded`` declares |x| < 2^15, which holds
+    for every InstanceNorm'ed volume.  A value below 2^-27 of its sample's maximum loses relative precision.
+
+    No call reads anything back to the host.  That includes the weight's range: the inference path's
+    |w| < 8 is not checked, and a weight whose 2^12-fold leaves f16's range (|w| >= 15.996) gives non-finite
+    outputs (its split halves are inf and -inf), which a loss's NaN rules catch.  ``check_weight=True`` runs
+    the blocking |w| < 8 check and raises instead; for debugging."""
+    for t, name in ((x, "x"), (weight, "weight")):
+        _on_gpu(t, name)
+    problem = _k3_problem(x, weight)
+    if problem is not None:
+        raise ValueError(f"conv3d_k3: {problem}")
+    if check_weight and not bool((weight.detach().abs() < 8.0).all()):
+        raise ValueError("conv3d_k3: a weight is outside the split range |w| < 8")
+    return _Conv3dK3Fn.apply(x.float().contiguous(), weight.float().contiguous(), bool(x_bounded))
+
+
+def _conv(conv, x, convs: str):
+    """A BasicConv's own conv: ``conv3d_k3`` with convs="hip" where it is a plain stride-1, pad-1 3x3x3
+    nn.Conv3d with equal channel counts that the kernel is built for (its input is a ``volume_close`` output,
+    so |x| <= sqrt(cells) < 2^15), else the module on torch."""
+    if (convs == "hip" and isinstance(conv, torch.nn.Conv3d) and conv.bias is None and conv.groups == 1
+            and tuple(conv.kernel_size) == (3, 3, 3) and tuple(conv.stride) == (1, 1, 1)
+            and tuple(conv.padding) == (1, 1, 1) and tuple(conv.dilation) == (1, 1, 1)
+            and conv.padding_mode == "zeros" and conv.in_channels == conv.out_channels
+            and x.is_cuda and _k3_problem(x, conv.weight) is None):
+        return conv3d_k3(x, conv.weight, x_bounded=True)
+    return conv(x)
+
+
+def _close_layer(conv_block, x, gate=None, conv_out=None, convs: str = "torch"):
+    """One BasicConv (its own nn.Conv3d unless its output ``conv_out`` is given, then the fused close) -> its
+    output volume."""
+    return volume_close(_conv(conv_block.conv, x, convs) if conv_out is None else conv_out, *(gate or (None, None)),
                         negative_slope=getattr(conv_block.act_fn, "negative_slope", 0.01),
                         eps=getattr(conv_block.norm_fn, "eps", 1e-5))
 
 
-def _close_gated(layers, att, x, feat_left, feat_right, first=None):
+def _close_gated(layers, att, x, feat_left, feat_right, first=None, convs: str = "torch"):
     """A Sequential of BasicConvs followed by a DoubleFeatureAtt: the gate goes into the last close when
     its maps are at the volume's resolution, else that close runs gate-less and the module's own
     interpolate-and-multiply follows.  ``first``: the first layer's conv output where a join made it
     (x is unused then)."""
     for k, layer in enumerate(list(layers)[:-1]):
-        x = _close_layer(layer, x, conv_out=first if k == 0 else None)
-    y = first if first is not None and len(layers) == 1 else layers[-1].conv(x)
+        # (a Sequential's first conv reads the caller's x, whose range nobody vouches for: on torch)
+        x = _close_layer(layer, x, conv_out=first if k == 0 else None, convs=convs if k > 0 else "torch")
+    y = first if first is not None and len(layers) == 1 else _conv(layers[-1].conv, x, convs if len(layers) > 1 else "torch")
     gl = torch.sigmoid(att.feat_att_left(feat_left))
     gr = torch.sigmoid(att.feat_att_right(feat_right))
     D, H, W = y.shape[2:]
@@ -633,7 +731,8 @@ def _close_gated(layers, att, x, feat_left, feat_right, first=None):
     return g * volume_close(y, **last)
 
 
-def hourglass_forward(hg, x, features_left, features_right, layout: str = "reference", joins: str = "torch"):
+def hourglass_forward(hg, x, features_left, features_right, layout: str = "reference", joins: str = "torch",
+                      convs: str = "torch"):
     """The live part of the reference's ``Hourglass.forward`` (hourglass.py:61-91) for fine-tuning: the
     module's own ``nn.Conv3d``s on torch / MIOpen, every InstanceNorm3d + LeakyReLU (+ the following
     DoubleFeatureAtt) as one ``volume_close``.  The deepest down layer and the first up-path step feed
@@ -645,25 +744,32 @@ def hourglass_forward(hg, x, features_left, features_right, layout: str = "refer
     reference's permutes (``types.MethodType(hourglass_forward, hg)`` replaces its forward);
     layout="volume" works on [B,C,W2,H,W1].  joins="torch": the two joins (trilinear up-sampling, ``cat``
     and the 1x1x1 conv) stay on torch; joins="hip": each runs as one ``upcat_conv`` where that is built
-    for its channels and sizes (the published 8-channel hourglass), else on torch."""
+    for its channels and sizes (the published 8-channel hourglass), else on torch.  convs="torch": every
+    ``nn.Conv3d`` on torch; convs="hip": each stride-1 3x3x3 conv with equal channel counts that follows a close
+    (six of the published hourglass's eight) runs as ``conv3d_k3(..., x_bounded=True)`` where that is built for
+    its channels and sizes, else on torch; the stride-2 convs stay on torch."""
     if layout not in ("reference", "volume"):
         raise ValueError(f"hourglass_forward: layout must be 'reference' or 'volume', got {layout!r}")
     if joins not in ("torch", "hip"):
         raise ValueError(f"hourglass_forward: joins must be 'torch' or 'hip', got {joins!r}")
+    if convs not in ("torch", "hip"):
+        raise ValueError(f"hourglass_forward: convs must be 'torch' or 'hip', got {convs!r}")
     ns = hg.number_of_scales
     if layout == "reference":
         x = x.permute(0, 1, 3, 2, 4).permute(0, 1, 4, 3, 2)
     orig = x
     downs = []
     for i in range(ns - 2):
-        x = _close_gated(hg.down_layers[i], hg.feature_atts[i], x, features_left[i + 1], features_right[i + 1])
+        x = _close_gated(hg.down_layers[i], hg.feature_atts[i], x, features_left[i + 1], features_right[i + 1],
+                         convs=convs)
         downs.append(x)
     i = ns - 3
     y = _join(hg.agg_layers[i][0].conv, downs[ns - 3 - i], downs[ns - 2 - i], True, joins)
     x = _close_gated(hg.agg_layers[i], hg.feature_atts_up[i], None, features_left[ns - 2 - i],
-                     features_right[ns - 2 - i], first=y)
+                     features_right[ns - 2 - i], first=y, convs=convs)
     y = _join(hg.final_agg[0].conv, orig, x, False, joins)
-    x = _close_gated(hg.final_agg, hg.final_feature_atts_up, None, features_left[0], features_right[0], first=y)
+    x = _close_gated(hg.final_agg, hg.final_feature_atts_up, None, features_left[0], features_right[0], first=y,
+                     convs=convs)
     if layout == "reference":
         x = x.permute(0, 1, 4, 3, 2).permute(0, 1, 3, 2, 4)
     return x

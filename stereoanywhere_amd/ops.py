@@ -561,6 +561,86 @@ def conv3d_pointwise_backward(x: torch.Tensor, grad: torch.Tensor, w_t: torch.Te
     return dx, dw
 
 
+# ------------------------------------------------------------------------------- 3x3x3 conv backward
+CONV3D_K3_CHANNELS = (8, 16, 32)   # Cin = Cout of sa_conv3d_mf(_scaled) and sa_conv3d_k3_backward_weight
+
+
+def sample_scale(t: torch.Tensor, rep: int = 1):
+    """Per sample b of t [B, ...] the power of two s_b = 2^k with max |t_b| s_b in [2^13, 2^14) (|k| <= 100),
+    1 for an all-zero sample or one that holds an inf or a NaN (sa_sample_scale): one launch after a memset,
+    no host sync.  Returns (scale [B * rep], every s_b rep times: rep = C is sa_conv3d_mf_scaled's in_rstd;
+    inv [B] = 1 / s_b)."""
+    _check(t, "t")
+    B = t.shape[0]
+    n = t.numel() // max(B, 1)
+    state = torch.empty((2 * B,), device=t.device, dtype=torch.int32)
+    scale = torch.empty((B * rep,), device=t.device, dtype=torch.float32)
+    inv = torch.empty((B,), device=t.device, dtype=torch.float32)
+    N.call("sa_sample_scale", t.data_ptr(), B, n, rep, state.data_ptr(), scale.data_ptr(), inv.data_ptr(), _stream(t))
+    return scale, inv
+
+
+def conv3d_mf_table(w_t: torch.Tensor) -> torch.Tensor:
+    """conv3d_mf_weights without its |w| < 8 check, which reads a tensor back to the host: the B-fragment
+    table of a [C][27][C] kernel, C in CONV3D_K3_CHANNELS.  A weight whose 2^12-fold leaves f16's range
+    (|w| >= 15.996) splits into hi = inf, lo = -inf, so every output it reaches is NaN."""
+    _check(w_t, "w_t")
+    cin, _, cout = w_t.shape
+    n = int(N.lib().sa_conv3d_mf_weights_size(cin, cout))
+    if n < 0:
+        raise ValueError(f"conv3d_mf_table: no kernel for {cin} -> {cout} (built: 8 -> 8, 16 -> 16, 32 -> 32)")
+    table = torch.empty((n,), device=w_t.device, dtype=torch.uint8)
+    N.call("sa_conv3d_mf_weights", w_t.data_ptr(), cin, cout, table.data_ptr(), _stream(table))
+    return table
+
+
+def conv3d_mf_scaled(x: torch.Tensor, table: torch.Tensor, in_scale: Optional[torch.Tensor] = None,
+                     out_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The stride-1 3x3x3 conv (pad 1, no bias) of x [B,C,D,H,W] itself, no norm and no activation, on the
+    split-f16 MFMA kernel (sa_conv3d_mf_scaled): in_scale [B*C] and out_scale [B] are sample_scale(x, C)'s two
+    results, which make the conv safe for an x of any range; None, None: the identity transform, for an x the
+    caller knows to be bounded (|x| < 2^15, as every InstanceNorm'ed volume is)."""
+    B, C, D, H, W = _close_dims(x, "x", "conv3d_mf_scaled")
+    if (in_scale is None) != (out_scale is None):
+        raise ValueError("conv3d_mf_scaled: give both scales or neither")
+    if in_scale is None:
+        in_scale = torch.ones((B * C,), device=x.device, dtype=torch.float32)
+        out_scale = torch.ones((B,), device=x.device, dtype=torch.float32)
+    mean = torch.zeros((B * C,), device=x.device, dtype=torch.float32)
+    out = torch.empty_like(x)
+    N.call("sa_conv3d_mf_scaled", x.data_ptr(), B, C, D, H, W, table.data_ptr(), C, mean.data_ptr(), in_scale.data_ptr(),
+           1.0, out_scale.data_ptr(), out.data_ptr(), None, _stream(x))
+    return out
+
+
+def conv3d_k3_backward_weight_work(C: int, B: int, D: int, H: int, W: int) -> int:
+    """Doubles of scratch sa_conv3d_k3_backward_weight needs; -1 where no kernel is built."""
+    return int(N.lib().sa_conv3d_k3_backward_weight_work(C, B, D, H, W))
+
+
+def conv3d_k3_backward_weight(x: torch.Tensor, grad: torch.Tensor, x_scale: Optional[torch.Tensor] = None,
+                              g_scale: Optional[torch.Tensor] = None, work: Optional[torch.Tensor] = None):
+    """dw [C][27][C] (ops.conv3d's [Cin][27][Cout]) = sum over samples and cells of x[ci, p + tap - 1] grad[co, p]
+    of a stride-1, pad-1 3x3x3 conv, x and grad [B,C,D,H,W] (sa_conv3d_k3_backward_weight).  x_scale / g_scale
+    [B]: sample_scale(., 1)[0] of the operand, None for one that is bounded (|v| < 2^15).  work: the float64
+    scratch (conv3d_k3_backward_weight_work doubles).  Deterministic."""
+    who = "conv3d_k3_backward_weight"
+    B, C, D, H, W = _close_dims(x, "x", who)
+    if _close_dims(grad, "grad", who) != (B, C, D, H, W):
+        raise RuntimeError(f"{who}: grad must have x's shape {(B, C, D, H, W)}, got {tuple(grad.shape)}")
+    count = conv3d_k3_backward_weight_work(C, B, D, H, W)
+    if count < 0:
+        raise RuntimeError(f"{who}: no kernel built for {C} -> {C} channels (built: 8 -> 8, 16 -> 16, 32 -> 32)")
+    if work is None:
+        work = torch.empty((count,), device=x.device, dtype=torch.float64)
+    elif work.dtype != torch.float64 or work.device != x.device or not work.is_contiguous() or work.numel() < count:
+        raise RuntimeError(f"{who}: work must hold {count} contiguous float64 on {x.device}")
+    dw = torch.empty((C, 27, C), device=x.device, dtype=torch.float32)
+    N.call("sa_conv3d_k3_backward_weight", x.data_ptr(), grad.data_ptr(), C, B, D, H, W, _ptr(x_scale), _ptr(g_scale),
+           work.data_ptr(), dw.data_ptr(), _stream(x))
+    return dw
+
+
 def _lookup_bytes(npix: int, nvol: int, num_levels: int, radius: int, cout: int) -> float:
     """Algorithmic bytes of one fused lookup: per pixel the coordinate, per volume the 2r + 2 cells
     of each level's window and the cout output planes."""
