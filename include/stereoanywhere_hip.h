@@ -404,7 +404,8 @@ int sa_lookup_get_shear_dual(void);
 long sa_shear_slice_size(int W1, int W2, int num_levels);
 long sa_shear_row_pitch(int W1);
 /* 1 when sa_corr_pyramid_shear + sa_corr_lookup_conv1x1_sheared take this geometry (B*H <= 65535,
- * W2 <= 511, 1..4 levels with the coarsest >= 2 wide), else 0: the caller keeps the row layout */
+ * W2 <= 511, 1..4 levels with the coarsest >= 2 wide, B*H*W1 <= 2^31 - 256 pixels), else 0: the caller keeps
+ * the row layout */
 int sa_corr_shear_supported(int B, int H, int W1, int W2, int num_levels);
 long sa_shear_level_offset(int W1, int W2, int num_levels, int level);
 int sa_corr_pyramid_shear(const float *pyramid, long row_stride, int B, int H, int W1, int W2,

@@ -256,8 +256,9 @@ __global__ __launch_bounds__(512) void conv2d_k3_narrow_kernel(const float *__re
 extern "C" int sa_conv2d_k3_narrow(const float *in, long in_bs, int B, int Cin, int H, int W, const float *weight,
                                    const float *bias, int Cout, float *out, long out_bs, void *stream) {
   SA_REQUIRE(in && weight && out, "sa_conv2d_k3_narrow: null pointer");
-  SA_REQUIRE(B > 0 && B <= 65535 && Cin > 0 && Cin % NW == 0 && H > 0 && W > 0, "sa_conv2d_k3_narrow: bad shape");
-  SA_REQUIRE((long)H * W < (1L << 31), "sa_conv2d_k3_narrow: plane too large");
+  SA_REQUIRE(B > 0 && B <= 65535 && Cin > 0 && Cin % NW == 0 && H > 0 && W > 0,
+             "sa_conv2d_k3_narrow: bad shape (B %d must be 1..65535, Cin %d a multiple of %d)", B, Cin, NW);
+  SA_REQUIRE((long)H * W < (1L << 31), "sa_conv2d_k3_narrow: plane too large (H*W = %ld must be below 2^31)", (long)H * W);
   dim3 grid((unsigned)((W + NCOL - 1) / NCOL), (unsigned)((H + NR - 1) / NR), (unsigned)B);
   hipStream_t s = sa::as_stream(stream);
   sa::TimingScope ts(SA_K_NARROW, s);

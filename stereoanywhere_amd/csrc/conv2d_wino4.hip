@@ -1225,7 +1225,8 @@ extern "C" int sa_flow_head_reduce(const float *part, int N, int Cout, int H, in
                                    void *stream) {
   SA_REQUIRE(part && bias0 && coords_x, "sa_flow_head_reduce: null pointer");
   const long per = sa_flow_head_part_size(1, Cout, H, W);
-  SA_REQUIRE(per > 0 && N > 0 && N <= 65535 && (long)H * W < (1L << 31), "sa_flow_head_reduce: bad shape");
+  SA_REQUIRE(per > 0 && N > 0 && N <= 65535 && (long)H * W < (1L << 31),
+             "sa_flow_head_reduce: bad shape (N %d must be 1..65535, H*W = %ld below 2^31)", N, (long)H * W);
   const int ltw = w4_ltw(H, W), bw = 4 << ltw, bh = 4 * (W4Big::NT >> ltw);
   const int tiles_w = (W + bw - 1) / bw, tiles_hw = tiles_w * ((H + bh - 1) / bh);
   const unsigned hw = (unsigned)((long)H * W);

@@ -520,7 +520,10 @@ static int conv_direct_launch(const float *in, long in_bs, int N, int Cin, int H
   SA_REQUIRE(!ds || out_ds, "sa_conv_direct: downsample weights without an output");
   SA_REQUIRE(K != 1 && pick(K, S, Cout, KC, NTL) && ds == (S == 2),
              "sa_conv_direct: no kernel for K=%d S=%d Cout=%d ds=%d", K, S, Cout, (int)ds);
-  SA_REQUIRE((long)Cin * H * W < (1L << 31), "sa_conv_direct: image too large");
+  // the kernel reads an image through a buffer resource: its record count and the patch offsets are 32-bit
+  // BYTE counts, and the out-of-range offset 0x7ffffff0 must lie past the records
+  SA_REQUIRE((long)Cin * H * W * 4 < 0x7ffffff0L,
+             "sa_conv_direct: image too large (Cin*H*W*4 = %ld bytes must be below 2^31 - 16)", (long)Cin * H * W * 4);
   SA_REQUIRE(Cin % KC == 0 || Cin <= KC, "sa_conv_direct: Cin must be a multiple of %d (or at most %d)", KC, KC);
   SA_REQUIRE(!cl || (cm && cs && K == 3 && Cin % KC == 0),
              "sa_conv_direct_close: needs mean / rstd, a 3x3 stride-2 conv and Cin %% %d == 0", KC);

@@ -339,7 +339,9 @@ extern "C" int sa_corr_shear_supported(int B, int H, int W1, int W2, int num_lev
   if ((long)B * H > 65535) return 0;
   if ((long)SH_J * (W2 + 1) * 4 > 64 * 1024) return 0;
   if (sa_pyramid_level_width(W2, num_levels - 1) < 2) return 0;
-  if ((long)B * H * W1 >= (1L << 31)) return 0;
+  // (the lookup kernels form blockIdx.x * 256 + threadIdx.x in 32 bits: the last block's lanes past the
+  // end must stay below 2^31 too, or they wrap negative and pass the p < npix test)
+  if ((long)B * H * W1 + 255 >= (1L << 31)) return 0;
   return 1;
 }
 
@@ -376,7 +378,9 @@ extern "C" int sa_corr_lookup_conv1x1_sheared(const float *sheared_a, const floa
              "sa_corr_lookup_conv1x1_sheared: level %d of width %d is too narrow to sample", num_levels - 1,
              sa_pyramid_level_width(W2, num_levels - 1));
   const long npix = (long)B * H * W1;
-  SA_REQUIRE(npix < (1L << 31), "sa_corr_lookup_conv1x1_sheared: too many pixels");
+  // the kernels' 32-bit pixel index of the last block's idle lanes (up to npix + 255) must not wrap
+  SA_REQUIRE(npix + 255 < (1L << 31), "sa_corr_lookup_conv1x1_sheared: too many pixels (B*H*W1 = %ld must be below 2^31 - 255)",
+             npix);
   const ShGeo sg = shear_geo(W1, W2, num_levels);
   ShLGeo g{};
   g.H = H;

@@ -735,6 +735,7 @@ extern "C" int sa_corr_pyramid_from_volume(const float *volume, long rows, int W
   SA_REQUIRE(num_levels >= 1 && num_levels <= 4, "sa_corr_pyramid_from_volume: num_levels must be 1..4");
   SA_REQUIRE(row_stride >= sa_pyramid_level_offset(W2, num_levels),
              "sa_corr_pyramid_from_volume: row_stride too small");
+  SA_REQUIRE((rows + 3) / 4 < (1L << 31), "sa_corr_pyramid_from_volume: grid too large (rows = %ld must be below 2^33 - 3)", rows);
   Geo g = make_geo(1, 1, 1, W2, num_levels, row_stride);
   hipStream_t s = sa::as_stream(stream);
   sa::TimingScope ts(SA_K_MONO_PYRAMID, s);
@@ -747,7 +748,7 @@ extern "C" int sa_corr_pyramid_from_volume_strided(const float *volume, int B, i
                                                    void *stream) {
   SA_REQUIRE(volume && pyramid, "sa_corr_pyramid_from_volume_strided: null pointer");
   SA_REQUIRE(B > 0 && B <= 65535 && H > 0 && H <= 65535 && W1 > 0 && W2 > 0,
-             "sa_corr_pyramid_from_volume_strided: bad shape");
+             "sa_corr_pyramid_from_volume_strided: bad shape (B %d and H %d must be 1..65535)", B, H);
   SA_REQUIRE(num_levels >= 1 && num_levels <= 4, "sa_corr_pyramid_from_volume_strided: num_levels must be 1..4");
   SA_REQUIRE(row_stride >= sa_pyramid_level_offset(W2, num_levels),
              "sa_corr_pyramid_from_volume_strided: row_stride too small");
@@ -782,7 +783,7 @@ extern "C" int sa_corr_pyramid_from_volume_strided_sheared(const float *volume, 
                                                            void *stream) {
   SA_REQUIRE(volume && sheared, "sa_corr_pyramid_from_volume_strided_sheared: null pointer");
   SA_REQUIRE(B > 0 && B <= 65535 && H > 0 && H <= 65535 && W1 > 0 && W2 > 0,
-             "sa_corr_pyramid_from_volume_strided_sheared: bad shape");
+             "sa_corr_pyramid_from_volume_strided_sheared: bad shape (B %d and H %d must be 1..65535)", B, H);
   SA_REQUIRE(num_levels >= 1 && num_levels <= 4,
              "sa_corr_pyramid_from_volume_strided_sheared: num_levels must be 1..4");
   SA_REQUIRE(W1 % 4 == 0 && sb % 4 == 0 && sh % 4 == 0 && sk % 4 == 0 && reinterpret_cast<uintptr_t>(volume) % 16 == 0,

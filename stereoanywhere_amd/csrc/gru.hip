@@ -383,8 +383,8 @@ extern "C" int sa_gru_zr(const float *xc, long xc_bs, const float *bx, const flo
                          const float *cr, long c_bs, const float *h, long h_bs, int B, int C, int HW,
                          float *z, float *rh, void *stream) {
   SA_REQUIRE(xc && hzr && cz && cr && h && z && rh, "sa_gru_zr: null pointer");
-  SA_REQUIRE(B > 0 && B <= 65535 && C > 0 && HW > 0, "sa_gru_zr: empty shape");
-  SA_REQUIRE((long)C * HW < (1L << 31), "sa_gru_zr: plane too large");
+  SA_REQUIRE(B > 0 && B <= 65535 && C > 0 && HW > 0, "sa_gru_zr: empty shape or B %d above 65535", B);
+  SA_REQUIRE((long)C * HW < (1L << 31), "sa_gru_zr: plane too large (C*HW = %ld must be below 2^31)", (long)C * HW);
   const unsigned per = (unsigned)((long)C * HW);
   const bool v4 = HW % 4 == 0 && al16(xc) && al16(hzr) && al16(cz) && al16(cr) && al16(h) && al16(z) && al16(rh) &&
                   xc_bs % 4 == 0 && hzr_bs % 4 == 0 && c_bs % 4 == 0 && h_bs % 4 == 0;
@@ -404,8 +404,8 @@ extern "C" int sa_gru_out_split(const float *xc, long xc_bs, const float *bx, co
                                 long qh_bs, const float *cq, long c_bs, const float *z, int B, int C, int HW, float *h,
                                 long h_bs, void *stream) {
   SA_REQUIRE(xc && qh && cq && z && h, "sa_gru_out: null pointer");
-  SA_REQUIRE(B > 0 && B <= 65535 && C > 0 && HW > 0, "sa_gru_out: empty shape");
-  SA_REQUIRE((long)C * HW < (1L << 31), "sa_gru_out: plane too large");
+  SA_REQUIRE(B > 0 && B <= 65535 && C > 0 && HW > 0, "sa_gru_out: empty shape or B %d above 65535", B);
+  SA_REQUIRE((long)C * HW < (1L << 31), "sa_gru_out: plane too large (C*HW = %ld must be below 2^31)", (long)C * HW);
   const unsigned per = (unsigned)((long)C * HW);
   const bool v4 = HW % 4 == 0 && al16(xc) && al16(qh) && (!qh2 || al16(qh2)) && al16(cq) && al16(z) && al16(h) &&
                   xc_bs % 4 == 0 && qh_bs % 4 == 0 && c_bs % 4 == 0 && h_bs % 4 == 0;
@@ -468,7 +468,8 @@ static bool band_shape(float sh, int Ho, int Wo, int &RB, size_t &lds) {
 extern "C" int sa_pool2x_p(const float *in, long in_bs, int in_pitch, int B, int C, int H, int W, float *out,
                            long out_bs, int out_pitch, void *stream) {
   SA_REQUIRE(in && out, "sa_pool2x: null pointer");
-  SA_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && (long)B * C <= 65535, "sa_pool2x: bad shape");
+  SA_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && (long)B * C <= 65535,
+             "sa_pool2x: bad shape (B*C = %ld planes must be 1..65535)", (long)B * C);
   const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   SA_REQUIRE(in_pitch >= W && out_pitch >= Wo, "sa_pool2x: row pitch below the width");
   SA_REQUIRE((long)H * in_pitch < (1L << 31) && (long)Ho * out_pitch < (1L << 31), "sa_pool2x: plane too large");
@@ -501,7 +502,7 @@ extern "C" int sa_interp_bilinear_ac_p(const float *in, long in_bs, int in_pitch
                                        int Wo, float *out, long out_bs, int out_pitch, void *stream) {
   SA_REQUIRE(in && out, "sa_interp_bilinear_ac: null pointer");
   SA_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && (long)B * C <= 65535,
-             "sa_interp_bilinear_ac: bad shape");
+             "sa_interp_bilinear_ac: bad shape (B*C = %ld planes must be 1..65535)", (long)B * C);
   SA_REQUIRE(in_pitch >= W && out_pitch >= Wo, "sa_interp_bilinear_ac: row pitch below the width");
   SA_REQUIRE((long)H * in_pitch < (1L << 31) && (long)Ho * out_pitch < (1L << 31),
              "sa_interp_bilinear_ac: plane too large");
@@ -550,7 +551,8 @@ extern "C" int sa_resample_multi(int njobs, const SaResampleJob *jobs, void *str
     SA_REQUIRE(q.in && q.out, "sa_resample_multi: null pointer");
     SA_REQUIRE(q.kind == SA_RESAMPLE_POOL2X || q.kind == SA_RESAMPLE_BILINEAR_AC || q.kind == SA_RESAMPLE_FLOW_X,
                "sa_resample_multi: unknown kind");
-    SA_REQUIRE(q.B > 0 && q.C > 0 && q.H > 0 && q.W > 0 && (long)q.B * q.C <= 65535, "sa_resample_multi: bad shape");
+    SA_REQUIRE(q.B > 0 && q.C > 0 && q.H > 0 && q.W > 0 && (long)q.B * q.C <= 65535,
+               "sa_resample_multi: bad shape (B*C = %ld planes must be 1..65535)", (long)q.B * q.C);
     int Ho = q.Ho, Wo = q.Wo;
     if (q.kind == SA_RESAMPLE_FLOW_X) {
       SA_REQUIRE(q.C == 1 && Ho == q.H && Wo == q.W && q.in_pitch == q.W && q.out_pitch == q.W &&
@@ -622,7 +624,8 @@ extern "C" int sa_interp_bilinear_ac(const float *in, long in_bs, int B, int C, 
 extern "C" int sa_relu_copy(const float *in, long in_bs, int B, int C, int HW, float *out, long out_bs,
                             void *stream) {
   SA_REQUIRE(in && out, "sa_relu_copy: null pointer");
-  SA_REQUIRE(B > 0 && B <= 65535 && C > 0 && HW > 0 && (long)C * HW < (1L << 31), "sa_relu_copy: bad shape");
+  SA_REQUIRE(B > 0 && B <= 65535 && C > 0 && HW > 0 && (long)C * HW < (1L << 31),
+             "sa_relu_copy: bad shape (B %d must be 1..65535, C*HW = %ld below 2^31)", B, (long)C * HW);
   const unsigned per = (unsigned)((long)C * HW);
   hipStream_t s = sa::as_stream(stream);
   sa::TimingScope ts(SA_K_PLUMBING, s);
@@ -633,7 +636,8 @@ extern "C" int sa_relu_copy(const float *in, long in_bs, int B, int C, int HW, f
 extern "C" int sa_flow_update(float *coords_x, const float *delta, long delta_bs, int B, int H, int W,
                               float *flow_a, long flow_a_bs, float *flow_b, long flow_b_bs, void *stream) {
   SA_REQUIRE(coords_x, "sa_flow_update: null coords");
-  SA_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && (long)H * W < (1L << 31), "sa_flow_update: bad shape");
+  SA_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && (long)H * W < (1L << 31),
+             "sa_flow_update: bad shape (B %d must be 1..65535, H*W = %ld below 2^31)", B, (long)H * W);
   const unsigned hw = (unsigned)((long)H * W);
   hipStream_t s = sa::as_stream(stream);
   sa::TimingScope ts(SA_K_PLUMBING, s);

@@ -657,6 +657,10 @@ extern "C" int sa_softargmin_conf(const float *vol_disp, const float *vol_conf, 
   SA_REQUIRE(B > 0 && H > 0 && W1 > 1 && W2 > 1, "sa_softargmin_conf: bad shape");
   SA_REQUIRE(sj == 1 || sk == 1, "sa_softargmin_conf: one of sj/sk must be 1");
   SA_REQUIRE(out_bs >= (long)H * (W1 > W2 ? W1 : W2), "sa_softargmin_conf: out_bs too small");
+  // a block per (b, h) slice, or per 1 to 256 lines of either side: the block counts are 32-bit
+  SA_REQUIRE((long)B * H * (W1 > W2 ? W1 : W2) < (1L << 31),
+             "sa_softargmin_conf: grid too large (B*H*max(W1, W2) = %ld lines must be below 2^31)",
+             (long)B * H * (W1 > W2 ? W1 : W2));
   SGeo g{H, W1, W2, sb, sh, sj, sk, out_bs, (float)std::log2((double)W1), (float)std::log2((double)W2)};
   hipStream_t s = sa::as_stream(stream);
   sa::TimingScope ts(SA_K_SOFTARGMIN, s);

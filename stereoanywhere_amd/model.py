@@ -416,11 +416,7 @@ class StereoAnywhere(nn.Module):
         trunc = (sm2, mirror) if a.use_truncate_vol else (None, None)
         # the sheared lookup for large volumes, where its kernels take the geometry (W4 <= 511,
         # B * H4 <= 65535 image rows); the row layout otherwise
-        big = (self.opts.sheared_lookup and B * H4 * W4 * W4 * 4 >= self.opts.shear_min_bytes
-               and ops.shear_supported(B, H4, W4, W4, a.corr_levels))
-        # (the producers that write the sheared layout themselves are exercised at 4 levels only:
-        # any other level count takes the row pyramid and the copy pass below)
-        direct = self.opts.sheared_producers and big and a.corr_levels == 4
+        big, direct = self._pyramid_route(B, H4, W4)
         if a.use_aggregate_stereo_vol:
             stereo_blk, ds2, ds3 = self._stereo_aggregate(dw, fmap2, fmap3, mde2, mde3, m2l, m3l, trunc, B, H4, W4,
                                                           full)
@@ -465,6 +461,18 @@ class StereoAnywhere(nn.Module):
         # stereoanywhere.py:299
         return (list(preds.unbind(0)), [None] * iters, [ds2, dm2, smde2], [ds3, dm3, smde3], [None, cf2, None],
                 [None, cf3, None])
+
+    def _pyramid_route(self, B, H4, W4):
+        """(big, direct): whether the lookups read disparity-sheared pyramids (large volumes whose geometry
+        ops.shear_supported takes; the row layout otherwise), and whether the producers write that layout
+        themselves."""
+        a = self.args
+        big = bool(self.opts.sheared_lookup and B * H4 * W4 * W4 * 4 >= self.opts.shear_min_bytes
+                   and ops.shear_supported(B, H4, W4, W4, a.corr_levels))
+        # (the producers that write the sheared layout themselves are exercised at 4 levels only:
+        # any other level count takes the row pyramid and the copy pass below)
+        direct = bool(self.opts.sheared_producers and big and a.corr_levels == 4)
+        return big, direct
 
     def _iterate_parts(self, parts, dw, hid, ctx, stereo_blk, mono_blk, coords_x, iters, B, H4, W4, preds=None):
         """The GRU loop over batch parts (pairs are independent), each on its own stream; the
